@@ -9,9 +9,13 @@ A step = clear the filter + build it from the device-resident key vector
 (bloomhip_set_batch).  With --gpus N every rank builds its own run on its own
 GPU (per-run sharding, no collective on the data path): weak scaling.
 
-Also reported at N=1: the C3 batched probe (16.7M GETs x 5 level filters),
-the end-to-end (host keys -> filter -> host bitmap) rate, and the CPU
-baseline (the oracle's C restatement, 1 thread) on the same keys.
+A plain run sets up, warms up, times the --steps steps, writes the last
+step's bitmap with --dump-outputs DIR, and prints the result line.  With
+--full it also checks the bitmap against its oracle pin, times every kernel
+in a pass of its own, and reports at N=1 the C3 batched probe (16.7M GETs x
+5 level filters), the other workloads' legs, the end-to-end (host keys ->
+filter -> host bitmap) rate, and the CPU baseline (the oracle's C
+restatement) on the same keys.
 
 Prints ONE JSON line on rank 0.
 """
@@ -273,6 +277,32 @@ def compute_ceiling(case, achieved):
             "frac": round(achieved / c["Gkeys_s"], 4),
             "hash3_mod_p2": d["hash3_mod_p2"].get(str(c["m"][0])),
             "source": f"{COMPUTE_CEILING} ({case}; from {d['source'].split(' ')[0]})"}
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # of the 64 MB a dump may take in all
+DUMP_SAMPLE_WORDS = 1 << 21   # 64-bit words sampled from a bitmap over the budget
+DUMP_SAMPLE_SEED = 13141
+
+
+def dump_outputs(out_dir, words):
+    """--dump-outputs: the bitmap the last timed step built (what a caller of
+    clear + set_batch receives from words()), as float32 .npy.  Every uint64
+    word is written as its four 16-bit parts, least significant first (exact
+    in float32): bitmap_u16.npy.  A bitmap that would take more than
+    DUMP_BUDGET_BYTES that way is sampled instead: DUMP_SAMPLE_WORDS word
+    indices drawn once from a fixed seed (bitmap_sample_index.npy, float64,
+    ascending) and those words' parts (bitmap_sample_u16.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    if words.size * 4 * 4 <= DUMP_BUDGET_BYTES:
+        np.save(os.path.join(out_dir, "bitmap_u16.npy"), words.view(np.uint16).astype(np.float32))
+        return
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+    idx = np.sort(rng.choice(words.size, size=DUMP_SAMPLE_WORDS, replace=False))
+    np.save(os.path.join(out_dir, "bitmap_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "bitmap_sample_u16.npy"),
+            np.ascontiguousarray(words[idx]).view(np.uint16).astype(np.float32))
 
 
 def load_pins():
@@ -784,6 +814,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--strategy", default="auto", choices=["auto", "atomic", "lds", "partition"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the bitmap of the last timed step to DIR/*.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also: the oracle check of the bitmap, the per-kernel pass, the "
+                         "secondary legs and the CPU baseline (the --no-* options trim these)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip probe/e2e legs")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 eight-run leg")
@@ -793,6 +828,9 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         log(f"--gpus must be >= 1 (got {args.gpus})")
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        log(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
         sys.exit(2)
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -841,13 +879,13 @@ def main():
     resolved = bh.STRATEGY_NAMES[f.resolve_strategy(n)]
     s = torch.cuda.current_stream()
 
-    # Validity: the bitmap a step produces is the oracle-pinned one.
+    # Validity (--full): the bitmap a step produces is the oracle-pinned one.
     f.clear(stream=s)
     f.set_batch(dkeys, stream=s)
     torch.cuda.synchronize()
     verified = None
     pins_path = os.path.join(ROOT, "tests", "golden", "pins.json")
-    if os.path.exists(pins_path):
+    if args.full and os.path.exists(pins_path):
         pins = json.load(open(pins_path))["oracle"]
         want = None
         if args.workload == "c2" and seed == W.SEED:
@@ -891,25 +929,34 @@ def main():
         elapsed = shard.max_over_ranks(elapsed, dist, device=coll_dev)
         dev_ms_per_step = shard.max_over_ranks(dev_ms_per_step, dist, device=coll_dev)
 
-    # Per-kernel device time: the same K steps again with every launch
-    # bracketed by HIP events on the launch stream (kept out of the timed
-    # loop above so event records do not perturb it).
-    f.profile(True)
-    f.profile_reset()
-    for _ in range(args.steps):
-        f.clear(stream=s)
-        f.set_batch(dkeys, stream=s)
-    torch.cuda.synchronize()
-    prof = f.profile_read()
-    f.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, f.words())
 
-    if dist:
-        all_ok = shard.all_ranks_ok(verified is not False, dist, device=coll_dev)
-    else:
-        all_ok = verified is not False
+    # Per-kernel device time (--full): the same K steps again with every
+    # launch bracketed by HIP events on the launch stream (kept out of the
+    # timed loop above so event records do not perturb it).
+    prof = {}
+    if args.full:
+        f.profile(True)
+        f.profile_reset()
+        for _ in range(args.steps):
+            f.clear(stream=s)
+            f.set_batch(dkeys, stream=s)
+        torch.cuda.synchronize()
+        prof = f.profile_read()
+        f.profile(False)
+
+    all_ok = None
+    if args.full:
+        if dist:
+            all_ok = shard.all_ranks_ok(verified is not False, dist, device=coll_dev)
+        else:
+            all_ok = verified is not False
 
     extras = {}
     cpu = None
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True
     if not args.no_extras and not args.no_c5:
         if rank == 0:
             log("C5 eight runs ...")
@@ -956,7 +1003,7 @@ def main():
                for k, v in prof.items()}
     build_ms = sum(v["ms"] / v["launches"] for k, v in prof.items() if k in BUILD_SLOTS)
     dominant = max((k for k in prof if k in BUILD_SLOTS),
-                   key=lambda k: prof[k]["ms"] / prof[k]["launches"])
+                   key=lambda k: prof[k]["ms"] / prof[k]["launches"], default=None)
     algo = 4 * n + (m + 63) // 64 * 8
     # The build is one unit of work done by its kernels in sequence (two for
     # the partition build), so the roofline is priced on the device time of a
@@ -971,6 +1018,7 @@ def main():
         "value": round(value, 4),
         "unit": "Gkeys/s",
         "n_gpus": world,
+        "full": args.full,
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 5),
@@ -988,7 +1036,7 @@ def main():
                      "traffic_source": (pmc or {}).get("file") if pmc and pmc.get("stale")
                      else (f"profiles/pmc_{args.workload}.json" if pmc else None),
                      "traffic_stale": bool(pmc and pmc.get("stale")),
-                     "kernel": "+".join(k for k in prof if k in BUILD_SLOTS),
+                     "kernel": "+".join(k for k in prof if k in BUILD_SLOTS) or None,
                      "dominant": dominant,
                      "algorithmic_bytes": algo,
                      "device_ms_per_build": round(dev_ms_per_step, 5),
@@ -1009,7 +1057,7 @@ def main():
                     "matches_sources": library_kernel_sha() == kernel_source_sha()},
         "cpu_baseline": cpu,
         "kernels": kernels,
-        "verified_vs_oracle": all_ok if verified is not None or dist else None,
+        "verified_vs_oracle": all_ok if verified is not None or (dist and args.full) else None,
     }
     line.update(extras)
     # Every BASELINE config this run exercised, with its oracle check (None:

@@ -82,8 +82,12 @@ def run_reference_test(name, tmp_path):
     t = REF_TESTS[name]
     for fname, hexdata in t["files"].items():
         (tmp_path / fname).write_bytes(bytes.fromhex(hexdata))
+    # the engine of this tree, wherever the binary was linked
+    env = dict(os.environ)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(
+        p for p in (bh.LIB_DIR, env.get("LD_LIBRARY_PATH")) if p)
     r = subprocess.run([LSM_BIN] + t["params"], input=dsl(t["ops"]), capture_output=True,
-                       text=True, cwd=tmp_path, timeout=120)
+                       text=True, cwd=tmp_path, timeout=120, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout == t["expected_stdout"]
 

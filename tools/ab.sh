@@ -2,7 +2,7 @@
 # A/B of two builds of libbloomhip on one GPU box, interleaved (B A B A ...)
 # so clock drift hits both alike.  A = cs265-lsm-tree_amd/lib_alt/libbloomhip.so
 # (build it from another commit with tools/build_alt.sh REV), B = the tree's
-# lib/libbloomhip.so.  Extra args go to bench.py.
+# lib/libbloomhip.so.  Extra args go to bench.py --full.
 # Usage: tools/ab.sh TAG ROUNDS [bench args...]
 set -o pipefail
 TAG=${1:?tag}; R=${2:-3}; shift 2
@@ -12,7 +12,7 @@ ALT=cs265-lsm-tree_amd/lib_alt/libbloomhip.so
 for r in $(seq 1 "$R"); do
   for v in B A; do
     if [ $v = A ]; then export BLOOMHIP_LIB=$PWD/$ALT; else unset BLOOMHIP_LIB; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > "$OUT/${v}_$r.log" 2>&1 || { echo "$v round $r failed"; tail -5 "$OUT/${v}_$r.log"; exit 1; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > "$OUT/${v}_$r.log" 2>&1 || { echo "$v round $r failed"; tail -5 "$OUT/${v}_$r.log"; exit 1; }
     python - "$OUT/${v}_$r.log" "$v" "$r" <<'PY'
 import json, sys
 d = json.loads(next(l for l in open(sys.argv[1]) if l.startswith("{")))

@@ -14,7 +14,7 @@ step() {  # name timeout cmd...
 }
 step pytest_gpu 900 python -u -m pytest tests -q -m gpu -x --timeout 300 --timeout-method thread || exit 1
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
-step bench 600 python bench.py || exit 1
+step bench 600 python bench.py --full || exit 1
 step bench_c4 400 python bench.py --workload c4 --steps 5 --warmup 1 --no-extras --no-cpu-baseline || exit 1
 step bench_c5 400 python bench.py --workload c5 --steps 20 --warmup 3 --no-extras --no-cpu-baseline || exit 1
 step stats_c2 400 rocprofv3 --kernel-trace --stats -d gpurun_out/ev/stats_c2 -o run --output-format csv -- python bench.py --steps 50 --warmup 10 --no-cpu-baseline || exit 1

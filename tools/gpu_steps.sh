@@ -26,7 +26,7 @@ for s in ${STEPS//,/ }; do
   case $s in
     pytest) run pytest 1200 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread || exit 1 ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench) run bench 600 python bench.py || exit 1 ;;
+    bench) run bench 600 python bench.py --full || exit 1 ;;
     bench_quick) run bench_quick 300 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline || exit 1 ;;
     bench_c4) run bench_c4 400 python bench.py --workload c4 --steps 5 --warmup 1 --no-extras --no-cpu-baseline || exit 1 ;;
     bench_c4w) run bench_c4w 400 python bench.py --workload c4w --steps 5 --warmup 1 --no-extras --no-cpu-baseline || exit 1 ;;
@@ -72,8 +72,8 @@ for s in ${STEPS//,/ }; do
     stats_route) run stats_route 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats_route" -o run --output-format csv -- python tools/probe_prof.py route 30 || exit 1 ;;
     stats_f10) run stats_f10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats_f10" -o run --output-format csv -- python tools/probe_prof.py auto 30 - f10 || exit 1 ;;
     stats_route_f10) run stats_route_f10 300 rocprofv3 --kernel-trace --stats -d "$OUT/stats_route_f10" -o run --output-format csv -- python tools/probe_prof.py route 30 - f10 || exit 1 ;;
-    bench_rep) run bench_rep1 600 python bench.py || exit 1
-               run bench_rep2 600 python bench.py || exit 1 ;;
+    bench_rep) run bench_rep1 600 python bench.py --full || exit 1
+               run bench_rep2 600 python bench.py --full || exit 1 ;;
     sq_route) for w in c3 f10; do
                 run sq_route_${w}_a 150 timeout -s KILL 140 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace -d "$OUT/sq_route_${w}_a" -o pmc --output-format csv -- python tools/probe_prof.py route 10 - $w || exit 1
                 run sq_route_${w}_b 150 timeout -s KILL 140 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace -d "$OUT/sq_route_${w}_b" -o pmc --output-format csv -- python tools/probe_prof.py route 10 - $w || exit 1
@@ -85,8 +85,8 @@ for s in ${STEPS//,/ }; do
             pmc c4 WRITE_SIZE --workload c4 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --prewarm-s 0 || exit 1 ;;
     pmc_c3) run pmc_c3_FETCH_SIZE 150 timeout -s KILL 140 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_c3_FETCH_SIZE" -o pmc --output-format csv -- python tools/probe_prof.py auto 10 || exit 1
             run pmc_c3_WRITE_SIZE 150 timeout -s KILL 140 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_c3_WRITE_SIZE" -o pmc --output-format csv -- python tools/probe_prof.py auto 10 || exit 1 ;;
-    bench_dist2) run bench_dist2 600 env BLOOMHIP_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --no-cpu-baseline || exit 1 ;;
-    bench_driver) run bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 || exit 1 ;;
+    bench_dist2) run bench_dist2 600 env BLOOMHIP_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --full --no-cpu-baseline || exit 1 ;;
+    bench_driver) run bench_driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full || exit 1 ;;
     cal) run cal 120 python tools/ubench.py cal || exit 1
          for c in FETCH_SIZE WRITE_SIZE "TCC_EA0_RDREQ_sum TCC_BUBBLE_sum TCC_EA0_RDREQ_32B_sum" \
                   "TCC_EA0_RDREQ_DRAM_sum TCC_EA0_WRREQ_DRAM_sum TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
