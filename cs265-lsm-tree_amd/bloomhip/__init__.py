@@ -46,7 +46,7 @@ PROBE_LDS = 3
 PROBE_STACKED = 4
 STRATEGY_NAMES = {BUILD_AUTO: "auto", BUILD_ATOMIC: "atomic", BUILD_LDS: "lds",
                   BUILD_PARTITION: "partition"}
-PROF_SLOTS = 12
+PROF_SLOTS = 13
 
 # Every symbol include/bloomhip.h and include/bloomhip_workload.h declare.
 EXPORTED_SYMBOLS = (
@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = (
     "bloomhip_gen_mt19937", "bloomhip_gen_glibc_rand", "bloomhip_gen_puts",
     "bloomhip_gen_workload", "bloomhip_set_batch_run", "bloomhip_set_run_meta",
     "bloomhip_get_run_meta", "bloomhip_route_gets", "bloomhip_route_gets_packed", "bloomhip_save", "bloomhip_load",
-    "bloomhip_build_from_run_file", "bloomhip_compact", "bloomhip_clone",
+    "bloomhip_build_from_run_file", "bloomhip_compact", "bloomhip_clone", "bloomhip_get_batch",
 )
 
 
@@ -138,6 +138,8 @@ def _lib():
                                           ctypes.POINTER(ctypes.c_int32)]),
             "bloomhip_route_gets": (I, [ctypes.POINTER(P), I, P, SZ, SZ, I, P, P, P, I, P]),
             "bloomhip_route_gets_packed": (I, [ctypes.POINTER(P), I, P, SZ, SZ, I, P, P, I, P]),
+            "bloomhip_get_batch": (I, [ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(SZ), I,
+                                       I, P, SZ, SZ, I, P, P, P, I, P]),
             "bloomhip_compact": (I, [ctypes.POINTER(P), P, I, I, I, P, ctypes.POINTER(SZ), I, P,
                                      I, P]),
             "bloomhip_save": (I, [P, ctypes.c_char_p]),
@@ -509,6 +511,54 @@ def unpack_route(route):
     first = np.where(none, -1, (r >> ROUTE_PAGE_BITS).astype(np.int32)).astype(np.int32)
     page = np.where(none, -1, (r & ((1 << ROUTE_PAGE_BITS) - 1)).astype(np.int32)).astype(np.int32)
     return first, page
+
+
+VAL_NONE = -2**31  # vals[i] when no run holds key i (= VAL_TOMBSTONE, src/types.h:12)
+
+
+def get_batch(runs: Sequence[BloomFilter], entries, keys, n: int | None = None, stride: int = 4,
+              vals=None, found_run=None, stats=None, stream=None):
+    """Batched GET (bloomhip_get_batch): runs newest first, entries[r] run r's
+    entry_t records (int32 [n_r, 2] numpy arrays or device tensors, keys
+    ascending).  Returns (vals int32[n], found_run int32[n], stats uint64
+    [nruns, 2]): the value and the run that holds each key (VAL_NONE and -1
+    when none does; a tombstone's value is passed through), and per run its
+    page reads and how many of them were false positives.  Outputs are
+    allocated on the host when none is given; pass device tensors for those
+    wanted to keep them on the device (the others are skipped)."""
+    ptr, on_dev, keep = _keys_ptr(keys, stride)
+    n = _key_count(keep, stride, n)
+    nr = len(runs)
+    if len(entries) != nr:
+        raise ValueError(f"{nr} runs but {len(entries)} entry arrays")
+    for e in entries:  # entry_t {int32 key; int32 val;} (src/types.h:14-22)
+        dt = str(e.dtype)
+        if dt not in ("int32", "torch.int32") or len(e.shape) != 2 or e.shape[1] != 2:
+            raise ValueError(f"entries must be int32 [n, 2] entry_t arrays (got {dt} {tuple(e.shape)})")
+    keeps = [_ptr_of(e) for e in entries]
+    sizes = [_nbytes(k[2]) // 8 for k in keeps]
+    ons = {k[1] for k, sz in zip(keeps, sizes) if sz}  # an empty run has no buffer to place
+    if len(ons) > 1:
+        raise ValueError("entries must be all host or all device buffers")
+    ent_dev = ons.pop() if ons else 0
+    if vals is None and found_run is None and stats is None:
+        vals = np.empty(n, dtype=np.int32)
+        found_run = np.empty(n, dtype=np.int32)
+        stats = np.zeros((nr, 2), dtype=np.uint64)
+    need = ((n * 4, 4, "vals"), (n * 4, 4, "found_run"), (nr * 16, 8, "stats"))
+    outs = [_out_ptr(x, *nd) if x is not None else (None, None, None)
+            for x, nd in zip((vals, found_run, stats), need)]
+    devs = {o[1] for o in outs if o[0] is not None}
+    if len(devs) > 1:
+        raise ValueError("get_batch outputs must be all host or all device buffers")
+    out_dev = devs.pop() if devs else 0
+    harr = (ctypes.c_void_p * max(nr, 1))(*[r.handle.value for r in runs])
+    earr = (ctypes.c_void_p * max(nr, 1))(*[k[0] if sz else None for k, sz in zip(keeps, sizes)])
+    ns = (ctypes.c_size_t * max(nr, 1))(*sizes)
+    _check(_lib().bloomhip_get_batch(harr, earr, ns, nr, ent_dev, ptr, n, stride, on_dev,
+                                     outs[0][0], outs[1][0], outs[2][0], out_dev,
+                                     _stream_ptr(stream)), "bloomhip_get_batch")
+    return vals, found_run, stats
 
 
 def compact(runs, drop_tombstones: bool = False, filter: BloomFilter | None = None,

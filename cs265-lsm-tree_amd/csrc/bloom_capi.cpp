@@ -85,11 +85,12 @@ enum ProfSlot {
     SLOT_PROBE_STACK = 9,
     SLOT_PROBE_STACK_ROUTE = 10,  // a stacked probe with GET routing fused into its combine
     SLOT_ROUTE = 11,              // k_route after the probes (routing not fused)
+    SLOT_GET_RESOLVE = 12,        // k_get_resolve: candidate runs to values (bloomhip_get_batch)
 };
 const char *kSlotNames[BLOOMHIP_PROF_SLOTS] = {
     "clear(memset)", "k_build_atomic", "k_build_lds",       "k_part_bin", "k_part_apply",
     "k_probe",       "probe_partitioned", "copy",           "k_probe_lds",  "probe_stacked",
-    "probe_stacked+route", "k_route",
+    "probe_stacked+route", "k_route", "k_get_resolve",
 };
 
 struct PendingTiming {
@@ -124,6 +125,12 @@ struct bloomhip_filter {
     uint32_t nfences = 0;
     void *d_route_stage = nullptr;  // first/page staging for host outputs
     size_t route_stage_bytes = 0;
+    // bloomhip_get_batch: host entries staged on the device; vals, found_run
+    // and stats staging for host outputs (or the candidate rows' scratch)
+    void *d_get_entries = nullptr;
+    size_t get_entries_bytes = 0;
+    void *d_get_stage = nullptr;
+    size_t get_stage_bytes = 0;
     // bloomhip_is_set's answer: a pinned host word mapped into the device
     // (allocated on the first scalar call)
     uint32_t *h_hit = nullptr;
@@ -554,6 +561,8 @@ int bloomhip_destroy(bloomhip_filter *f) {
     if (f->d_out_stage) (void)hipFree(f->d_out_stage);
     if (f->d_meta) (void)hipFree(f->d_meta);
     if (f->d_route_stage) (void)hipFree(f->d_route_stage);
+    if (f->d_get_entries) (void)hipFree(f->d_get_entries);
+    if (f->d_get_stage) (void)hipFree(f->d_get_stage);
     if (f->h_hit) (void)hipHostFree(f->h_hit);
     (void)hipStreamDestroy(f->stream);
     delete f;
@@ -969,6 +978,43 @@ int bloomhip_test_batch(const bloomhip_filter *const *filters, int nf, const voi
 
 namespace {
 
+// The routing of n device-resident keys over nruns runs, enqueued on s (every
+// handle's lock held): the runs' metadata into *t, their filters probed into
+// dcand (nruns x ceil(n/64)), and the rows range-checked and the route outputs
+// written either by the stacked probe's combine (when one stack takes every
+// run) or by k_route.  Shared by the routing calls and bloomhip_get_batch.
+int route_rows(bloomhip_filter *f0, const bloomhip_filter *const *runs, int nruns,
+               const KeySpan &ks, size_t n, uint64_t *dcand, const RouteOut &ro, hipStream_t s,
+               RouteTable *t) {
+    int rc = materialize_all(runs, nruns, s);
+    if (rc) return rc;
+    *t = RouteTable{};
+    t->nruns = nruns;
+    uint32_t off = 0;
+    for (int j = 0; j < nruns; j++) {
+        bloomhip_filter *fj = const_cast<bloomhip_filter *>(runs[j]);
+        if (!fj->d_meta) {  // no metadata: never a candidate
+            rc = meta_reserve(fj, 0);
+            if (rc) return rc;
+            fj->nfences = 0;
+        }
+        t->meta[j] = fj->d_meta;
+        t->nfences[j] = fj->nfences;
+        t->fence_off[j] = off;
+        off += fj->nfences;
+    }
+    t->total_fences = off;
+    const size_t nw = (n + 63) / 64;
+    FusedRoute fr{t, ro, false};
+    rc = probe_rows(f0, runs, nruns, ks, n, dcand, s, &fr);
+    if (rc) return rc;
+    if (!fr.routed) {  // the filters were probed apart: route over their rows
+        hipError_t e = timed(f0, SLOT_ROUTE, s, [&] { return launch_route(ks, *t, dcand, nw, ro, s); });
+        if (e != hipSuccess) return fail_hip(e, "k_route launch");
+    }
+    return BLOOMHIP_OK;
+}
+
 // bloomhip_route_gets and bloomhip_route_gets_packed: the candidate rows and
 // either first / page or their packed form (each output optional).
 int route_impl(const bloomhip_filter *const *runs, int nruns, const void *keys, size_t n,
@@ -987,24 +1033,7 @@ int route_impl(const bloomhip_filter *const *runs, int nruns, const void *keys, 
     KeySpan ks{};
     int rc = device_keys(f0, keys, n, stride_bytes, keys_on_device, s, &ks);
     if (rc) return rc;
-    rc = materialize_all(runs, nruns, s);
-    if (rc) return rc;
     RouteTable t{};
-    t.nruns = nruns;
-    uint32_t off = 0;
-    for (int j = 0; j < nruns; j++) {
-        bloomhip_filter *fj = const_cast<bloomhip_filter *>(runs[j]);
-        if (!fj->d_meta) {  // no metadata: never a candidate
-            rc = meta_reserve(fj, 0);
-            if (rc) return rc;
-            fj->nfences = 0;
-        }
-        t.meta[j] = fj->d_meta;
-        t.nfences[j] = fj->nfences;
-        t.fence_off[j] = off;
-        off += fj->nfences;
-    }
-    t.total_fences = off;
     const size_t nw = (n + 63) / 64;
     const size_t cand_bytes = (size_t)nruns * nw * 8;
     uint64_t *dcand = out_on_device ? cand_packed : nullptr;
@@ -1022,13 +1051,8 @@ int route_impl(const bloomhip_filter *const *runs, int nruns, const void *keys, 
         ro.page = page ? stage + n : nullptr;
         ro.packed = packed ? reinterpret_cast<uint32_t *>(stage) : nullptr;
     }
-    FusedRoute fr{&t, ro, false};
-    rc = probe_rows(f0, runs, nruns, ks, n, dcand, s, &fr);
+    rc = route_rows(f0, runs, nruns, ks, n, dcand, ro, s, &t);
     if (rc) return rc;
-    if (!fr.routed) {  // the filters were probed apart: route over their rows
-        hipError_t e = timed(f0, SLOT_ROUTE, s, [&] { return launch_route(ks, t, dcand, nw, ro, s); });
-        if (e != hipSuccess) return fail_hip(e, "k_route launch");
-    }
     if (!out_on_device) {
         if (cand_packed)
             HIP_TRY(hipMemcpyAsync(cand_packed, dcand, cand_bytes, hipMemcpyDeviceToHost, s));
@@ -1056,6 +1080,108 @@ int bloomhip_route_gets_packed(const bloomhip_filter *const *runs, int nruns, co
                                void *stream) {
     return route_impl(runs, nruns, keys, n, stride_bytes, keys_on_device, cand_packed, nullptr,
                       nullptr, route, out_on_device, stream);
+}
+
+namespace {
+
+// The interval search of k_get_resolve: kGetInterpolateDefault, unless
+// BLOOMHIP_GET_SEARCH = interp | binary picks the form (tools/get_bench.py
+// times one against the other; the tests run both).  Both are exact.
+bool get_search_interpolates() {
+    const char *e = getenv("BLOOMHIP_GET_SEARCH");
+    if (e && !strcmp(e, "interp")) return true;
+    if (e && !strcmp(e, "binary")) return false;
+    return kGetInterpolateDefault;
+}
+
+}  // namespace
+
+int bloomhip_get_batch(const bloomhip_filter *const *runs, const void *const *entries,
+                       const size_t *nentries, int nruns, int entries_on_device, const void *keys,
+                       size_t n, size_t stride_bytes, int keys_on_device, int32_t *vals,
+                       int32_t *found_run, uint64_t *stats, int out_on_device, void *stream) {
+    g_last_error.clear();
+    if (!runs || !entries || !nentries || nruns <= 0 || nruns > kMaxRouteRuns) return BLOOMHIP_EINVAL;
+    if ((n && !keys) || stride_bytes < 4 || stride_bytes % 4) return BLOOMHIP_EINVAL;
+    size_t total_entries = 0;
+    for (int j = 0; j < nruns; j++) {
+        if (!runs[j] || runs[j]->device != runs[0]->device) return BLOOMHIP_EINVAL;
+        if (nentries[j] && !entries[j]) return BLOOMHIP_EINVAL;
+        // entry_t records are read as 8-byte words on the device
+        if (reinterpret_cast<uintptr_t>(entries[j]) & (entries_on_device ? 7 : 3)) return BLOOMHIP_EINVAL;
+        total_entries += nentries[j];
+    }
+    bloomhip_filter *f0 = const_cast<bloomhip_filter *>(runs[0]);
+    DeviceGuard g(f0->device);
+    HandleLocks locks(runs, nruns);
+    // A run with fences must have the entries its fences describe: page <
+    // nfences then means page * 4096 < nentries, and with the kernel's clamps
+    // no read leaves the run.  A run without fences is never a candidate.
+    for (int j = 0; j < nruns; j++) {
+        const size_t nf = runs[j]->nfences;
+        if (nf && nf != (nentries[j] + kFenceStride - 1) / kFenceStride) return BLOOMHIP_EINVAL;
+    }
+    hipStream_t s = pick_stream(f0, stream);
+    const size_t stats_bytes = (size_t)nruns * 2 * sizeof(uint64_t);
+    if (n == 0) {
+        if (stats && out_on_device) HIP_TRY(hipMemsetAsync(stats, 0, stats_bytes, s));
+        else if (stats) memset(stats, 0, stats_bytes);
+        return BLOOMHIP_OK;
+    }
+    KeySpan ks{};
+    int rc = device_keys(f0, keys, n, stride_bytes, keys_on_device, s, &ks);
+    if (rc) return rc;
+    GetTable gt{};
+    if (entries_on_device) {
+        for (int j = 0; j < nruns; j++) {
+            gt.entries[j] = entries[j];
+            gt.nentries[j] = nentries[j];
+        }
+    } else {
+        HIP_TRY(grow(&f0->d_get_entries, &f0->get_entries_bytes, total_entries * 8));
+        char *dst = reinterpret_cast<char *>(f0->d_get_entries);
+        for (int j = 0; j < nruns; j++) {
+            gt.entries[j] = dst;
+            gt.nentries[j] = nentries[j];
+            if (nentries[j]) {
+                hipError_t e = timed(f0, SLOT_COPY, s, [&] {
+                    return hipMemcpyAsync(dst, entries[j], nentries[j] * 8, hipMemcpyHostToDevice, s);
+                });
+                if (e != hipSuccess) return fail_hip(e, "hipMemcpyAsync(entries H2D)");
+            }
+            dst += nentries[j] * 8;
+        }
+    }
+    const size_t nw = (n + 63) / 64;
+    HIP_TRY(grow(&f0->d_out_stage, &f0->out_stage_bytes, (size_t)nruns * nw * 8));
+    uint64_t *dcand = reinterpret_cast<uint64_t *>(f0->d_out_stage);
+    int32_t *dvals = vals, *dfound = found_run;
+    uint64_t *dstats = stats;
+    if (!out_on_device && (vals || found_run || stats)) {
+        HIP_TRY(grow(&f0->d_get_stage, &f0->get_stage_bytes, n * 8 + stats_bytes));
+        int32_t *stage = reinterpret_cast<int32_t *>(f0->d_get_stage);
+        dvals = vals ? stage : nullptr;
+        dfound = found_run ? stage + n : nullptr;
+        dstats = stats ? reinterpret_cast<uint64_t *>(stage + 2 * n) : nullptr;
+    }
+    if (dstats) HIP_TRY(hipMemsetAsync(dstats, 0, stats_bytes, s));
+    // Stage one: the routing, for its range-checked candidate rows only.
+    RouteTable t{};
+    rc = route_rows(f0, runs, nruns, ks, n, dcand, RouteOut{}, s, &t);
+    if (rc) return rc;
+    // Stage two: candidates to values.
+    const bool interp = get_search_interpolates();
+    hipError_t e = timed(f0, SLOT_GET_RESOLVE, s, [&] {
+        return launch_get_resolve(ks, t, gt, dcand, nw, dvals, dfound, dstats, interp, s);
+    });
+    if (e != hipSuccess) return fail_hip(e, "k_get_resolve launch");
+    if (!out_on_device) {
+        if (vals) HIP_TRY(hipMemcpyAsync(vals, dvals, n * 4, hipMemcpyDeviceToHost, s));
+        if (found_run) HIP_TRY(hipMemcpyAsync(found_run, dfound, n * 4, hipMemcpyDeviceToHost, s));
+        if (stats) HIP_TRY(hipMemcpyAsync(stats, dstats, stats_bytes, hipMemcpyDeviceToHost, s));
+    }
+    if (!keys_on_device || !entries_on_device || !out_on_device) HIP_TRY(hipStreamSynchronize(s));
+    return BLOOMHIP_OK;
 }
 
 int bloomhip_set(bloomhip_filter *f, int32_t key) {

@@ -74,6 +74,17 @@ struct RouteTable {
     uint32_t total_fences;
     int nruns;
 };
+// The runs' entries for the batched GET (k_get_resolve): run r's entry_t
+// {key, val} records (src/types.h:14-22) on the device, keys ascending.
+struct GetTable {
+    const void *entries[kMaxRouteRuns];
+    uint64_t nentries[kMaxRouteRuns];
+};
+// k_get_resolve's interval search: whether it guesses from the interval's
+// fences before it halves.  At C3 (16.8M GETs, 11.4M page reads) the kernel
+// took 1.71 ms with the plain binary search and 0.95 ms with the guess
+// (DESIGN.md §9 has the figures and the form in between).
+constexpr bool kGetInterpolateDefault = true;
 
 // LDS bytes a private-bitmap workgroup may use (m/8 must fit): 160 KiB per
 // CU on gfx950, one such workgroup per CU.
@@ -333,6 +344,17 @@ hipError_t launch_run_meta_sorted(const KeySpan &keys, int32_t *meta, hipStream_
 // newest candidate run and its page index per key (first/page may be null).
 hipError_t launch_route(const KeySpan &keys, const RouteTable &t, uint64_t *cand, size_t nw,
                         const RouteOut &ro, hipStream_t stream);
+// Batched GET past routing (bloom_get.hip): cand holds the range-checked
+// candidate rows that routing left (nw words per row).  Per key, the newest
+// candidate run whose fence interval holds it: its index to found, the
+// entry's value to vals (-1 and INT32_MIN when none does); stats[2r] += page
+// reads of run r, stats[2r + 1] += those that did not hold the key (the
+// caller zeroes stats).  vals, found and stats may each be null.
+// interpolate: the interval search guesses from the interval's fences before
+// it halves (exact either way).
+hipError_t launch_get_resolve(const KeySpan &keys, const RouteTable &t, const GetTable &g,
+                              const uint64_t *cand, size_t nw, int32_t *vals, int32_t *found,
+                              uint64_t *stats, bool interpolate, hipStream_t stream);
 // Partitioned probe of one filter (nbins as plan_segments): bin the
 // keys' positions by segment (recording each position's sorted slot), test
 // each segment in LDS writing one result byte per sorted entry, then AND each

@@ -155,7 +155,8 @@ int bloomhip_get_run_meta(const bloomhip_filter *f, int32_t *fences, size_t cap,
  *                the key is there, src/lsm_tree.cpp:195-201), -1 if none;
  *   page[i]      that run's page index, upper_bound(fences, key) - 1
  *                (src/run.cpp:97-99), -1 if none.
- * Reading the page and checking the key stays with the caller. */
+ * Reading the page and checking the key stays with the caller, or goes to
+ * bloomhip_get_batch below. */
 int bloomhip_route_gets(const bloomhip_filter *const *runs, int nruns, const void *keys,
                         size_t n, size_t stride_bytes, int keys_on_device,
                         uint64_t *cand_packed, int32_t *first_run, int32_t *page,
@@ -172,6 +173,48 @@ int bloomhip_route_gets_packed(const bloomhip_filter *const *runs, int nruns, co
                                size_t n, size_t stride_bytes, int keys_on_device,
                                uint64_t *cand_packed, uint32_t *route, int out_on_device,
                                void *stream);
+
+/* Batched GET, whole (LSMTree::get past the buffer, src/lsm_tree.cpp:173-215;
+ * Run::get, src/run.cpp:85-113): routing as bloomhip_route_gets, then the
+ * candidate runs are read on the device until one holds the key.  runs[0] is
+ * the newest, nruns <= 64, all on one device.
+ * entries[r]: run r's entry_t {int32 key; int32 val;} records, keys strictly
+ * ascending (as a flush or bloomhip_compact writes them), nentries[r] of them,
+ * on runs' device when entries_on_device (8-byte aligned); host entries are
+ * staged to the device inside the call.
+ * Per key i, newest run first: run r is read when it is a routing candidate
+ * (fence_r[0] <= key <= max_key_r && is_set_r(key)); its page is
+ * upper_bound(fences, key) - 1, and the entries searched are that fence
+ * interval, [page * 4096, min((page + 1) * 4096, nentries[r])).  If the key
+ * is there, found_run[i] = r and vals[i] = its value, VAL_TOMBSTONE
+ * (INT32_MIN) included: a tombstone in a newer run hides older values
+ * (src/lsm_tree.cpp:214).  If not, the read was a false positive and the next
+ * candidate run is visited.  No run holds the key: found_run[i] = -1 and
+ * vals[i] = INT32_MIN, so vals[i] != INT32_MIN is exactly "the reference
+ * prints a value".
+ * stats (optional, 2 * nruns u64, overwritten by every call; zeros when
+ * n == 0): stats[2r] = page reads of run r, stats[2r + 1] = how many of those
+ * did not hold the key.  vals and found_run are optional too (NULL to skip).
+ * Outputs are all host or all device.  Asynchronous when keys, entries and
+ * outputs are all device-resident; otherwise the stream is synchronised
+ * before the call returns.
+ * BLOOMHIP_EINVAL: NULLs where data is required, nentries[r] > 0 with
+ * entries[r] NULL, or a run with fences whose entries do not fit them
+ * (nfences != ceil(nentries[r] / 4096)); a run without fences is never a
+ * candidate and may have any entries.  With that check and the kernel's
+ * clamping of every entry index to [0, nentries[r]), entries that disagree
+ * with a run's metadata give unspecified answers but no access outside them.
+ * Deviation from the reference: Run::put places a fence every 4096 ENTRIES
+ * (src/run.cpp:164) while Run::get reads 4096 BYTES at byte offset
+ * page * 4096 (:101-103): 512 entries, at the wrong place for any page > 0,
+ * slots past the run's size included.  Here the interval
+ * the fences describe is searched; for runs of at most 512 entries the two
+ * agree on every stored key. */
+int bloomhip_get_batch(const bloomhip_filter *const *runs, const void *const *entries,
+                       const size_t *nentries, int nruns, int entries_on_device,
+                       const void *keys, size_t n, size_t stride_bytes, int keys_on_device,
+                       int32_t *vals, int32_t *found_run, uint64_t *stats,
+                       int out_on_device, void *stream);
 
 /* --- persistence beside the run -------------------------
  * The reference keeps a run's entries in an mmap'd file (src/run.cpp:34-72)
@@ -245,7 +288,7 @@ int bloomhip_resolve_strategy(const bloomhip_filter *f, size_t n, int *strategy_
  * is bracketed by HIP events on its stream; bloomhip_profile_read returns,
  * for kernel slot `slot` (0..BLOOMHIP_PROF_SLOTS-1), its name, launch count
  * and summed device milliseconds (it synchronises the stream). */
-#define BLOOMHIP_PROF_SLOTS 12
+#define BLOOMHIP_PROF_SLOTS 13
 int bloomhip_profile_enable(bloomhip_filter *f, int enable);
 int bloomhip_profile_read(bloomhip_filter *f, int slot, const char **name_out,
                           uint64_t *launches_out, double *ms_out);
