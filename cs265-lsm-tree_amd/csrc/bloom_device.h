@@ -273,11 +273,12 @@ __device__ __forceinline__ void nt_store16(uint4 *p, const uint4 &v) {
 
 // ABL (micro-benchmarks only, tools/ubench.py p1abl: the pass's cost by
 // stage): 0 the whole tile; 1 hash + bin and entry only; 2 + the rank
-// atomics; 3 + the scan and the run table; 4 + the scatter; 5 + the packing,
+// atomics; 3 + the scan and the run table; 4 + the scatter (each thread reads
+// one word of the image, or the compiler drops the stage); 5 + the packing,
 // without the sorted tile's stores.  A stage's unconsumed results go to one
 // store that only an impossible value takes.
 template <int LAYOUT, bool SLOTS, bool COLS, int TB, int MK, int MAXB = 0, int MINW = 4,
-          int ABL = 0, bool NT = false>
+          int ABL = 0, bool NT = false, bool DEFER = false>
 __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                                                        uint64_t *__restrict__ pos_out,
                                                        uint32_t *__restrict__ runs, SegMap sm,
@@ -301,27 +302,85 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
     const int per = (nb + 1 + TB - 1) / TB;  // this launch's scan entries per thread
     int32_t kcur[kPartKPT], knext[kPartKPT];
 
+    // Write-out of a sorted tile (its LDS image complete: after the tile's
+    // post-scatter barrier), one 16-B vector per call: the image goes out
+    // packed, three entries per u64; thread t packs entries 6v .. 6v+5 of
+    // vector v = r * TB + t.  In a short tile the entries past its end are
+    // stale, masked so they cannot spill into a neighbour field (pass 2 never
+    // uses them).
+    constexpr int kVecs = kTileKeys / 2;  // 16-B vectors per tile
+    constexpr int kStores = kVecs / TB;
+    static_assert(kStores * TB == kVecs && kStores * 2 == kPartKPT, "whole vectors per thread");
+    auto pack_store = [&](auto full_c, int r, size_t tile, int tile_keys) {
+        constexpr bool FULL = decltype(full_c)::value;
+        uint4 *dst = reinterpret_cast<uint4 *>(pos_out + tile * (size_t)kTileKeys) + r * TB + tid;
+        const uint2 *src = reinterpret_cast<const uint2 *>(s_sorted + 6 * (r * TB + tid));
+        const uint2 a = src[0], b = src[1], c = src[2];
+        uint32_t e[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
+        if constexpr (!FULL) {
+            // past the tile's positions: 0, not stale (the ladder probe's
+            // pass 2 reads with every entry of a vector, its run's or not)
+#pragma unroll
+            for (int q = 0; q < 6; q++) e[q] = 6 * (r * TB + tid) + q < 3 * tile_keys ? e[q] & kEntryMask : 0u;
+        }
+        // (a << s) | b is one v_lshl_or_b32; the compiler emitted a shift
+        // and an or for each (5 instead of 3 per u64)
+        const uint4 v = make_uint4(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11),
+                                   lshl_or(e[4], 21, e[3]), lshl_or(e[5], 10, e[4] >> 11));
+        if constexpr (ABL == 0) {
+            // NT: sorted tiles beyond the Infinity Cache (C5: 512 MiB) are
+            // stored non-temporal, so they do not evict what pass 2 can use
+            // there (C5 build 0.419 -> 0.406 ms; below it, C2's 128 MiB,
+            // pass 2 reads them from the cache: 35 us, 48 from HBM; a
+            // runtime choice in the kernel spilled 3-4 VGPRs)
+            if constexpr (NT) nt_store16(dst, v);
+            else *dst = v;
+        } else {
+            // keep the packing: a store only when an impossible value shows
+            if (v.x == 0xFFFFFFFFu && v.y == 0xFFFFFFFFu) *dst = v;
+        }
+    };
+    constexpr bool kPacks = ABL == 0 || ABL == 5;  // the stages that write tiles out
+
     // One tile.  FULL (every tile but a short last one) makes the key count a
     // constant: no per-key guards, and a fixed number of vector-memory ops
     // after the next tile's key loads, so the wait for those keys at the top
     // of the next tile is vmcnt(#stores) instead of a drain of every store.
     // Those loads are issued after the run-start stores for that reason.
-    auto do_tile = [&](auto full_c, size_t tile, size_t next) {
+    //
+    // DEFER (the 1024-thread builds, where a CU holds one workgroup and every
+    // barrier phase idles the whole CU): a tile's write-out does not follow
+    // its scatter, where the VALU has nothing else to do; it runs inside the
+    // hash phase of the workgroup's next tile, one vector after every second
+    // key (PREV: this tile carries the write-out of tile `prev`, always a
+    // FULL one, since only a block's last tile can be short), and after the
+    // block's last tile in an epilogue.  That is safe because s_sorted holds
+    // tile t from the post-scatter barrier of iteration t; it is next written
+    // by the scatter of t+1, which lies behind the hist-init, post-rank and
+    // two scan barriers of iteration t+1; and the rank atomics between the
+    // first two of those touch s_hist only.
+    auto do_tile = [&](auto full_c, auto prev_c, size_t tile, size_t next, size_t prev) {
         constexpr bool FULL = decltype(full_c)::value;
+        constexpr bool PREV = decltype(prev_c)::value && kPacks;
         const size_t tile0 = tile * kTileKeys;
         const int tile_keys = FULL ? (int)kTileKeys : (int)min((size_t)kTileKeys, ks.n - tile0);
         auto live = [&](int j) { return FULL || kPartKPT * tid + j < tile_keys; };
 #pragma clang loop unroll(disable) vectorize(disable)
         for (int b = tid; b <= nb; b += TB) s_hist[b] = (uint32_t)b << kBinShift;
-        lds_barrier();  // also: the previous tile's s_sorted reads are done
+        lds_barrier();  // also (!DEFER): the previous tile's s_sorted reads are done
 
         // 1. positions -> (segment, rank in segment) and the entry; the ranks
         //    are not consumed before the barrier, so all 24 LDS atomics of a
-        //    thread stay in flight behind the hashing.
+        //    thread stay in flight behind the hashing.  (PREV) the previous
+        //    tile's vectors go out here, one after every second key: all
+        //    four at the head spilled 3 VGPRs at 1024 threads.
         uint32_t br[kPartKPT * 3];   // (segment << kBinShift) + 4 * rank
         uint32_t ent[kPartKPT * 3];  // low kEntryBits bits of the position
 #pragma unroll
         for (int j = 0; j < kPartKPT; j++) {
+            if constexpr (PREV) {
+                if (j & 1) pack_store(BoolC<true>{}, j / 2, prev, kTileKeys);
+            }
             if (live(j)) {
                 const int32_t k = kcur[j];
 #pragma unroll
@@ -437,67 +496,74 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
             }
         }
         lds_barrier();
-        if constexpr (ABL == 4) return;
-        // 4. the sorted tile goes out packed, three entries per u64, as 16-B
-        //    stores: thread t packs entries 6v .. 6v+5 for its vectors v.  In
-        //    a short tile the entries past its end are stale, masked so they
-        //    cannot spill into a neighbour field (pass 2 never uses them).
-        uint4 *dst = reinterpret_cast<uint4 *>(pos_out + tile * (size_t)kTileKeys);
-        constexpr int kVecs = kTileKeys / 2;  // 16-B vectors per tile
-        constexpr int kStores = kVecs / TB;
-        static_assert(kStores * TB == kVecs, "whole vectors per thread");
-        uint4 v[kStores];
-#pragma unroll
-        for (int r = 0; r < kStores; r++) {
-            const uint2 *src = reinterpret_cast<const uint2 *>(s_sorted + 6 * (r * TB + tid));
-            const uint2 a = src[0], b = src[1], c = src[2];
-            uint32_t e[6] = {a.x, a.y, b.x, b.y, c.x, c.y};
-            if constexpr (!FULL) {
-                // past the tile's positions: 0, not stale (the ladder probe's
-                // pass 2 reads with every entry of a vector, its run's or not)
-#pragma unroll
-                for (int q = 0; q < 6; q++) e[q] = 6 * (r * TB + tid) + q < 3 * tile_keys ? e[q] & kEntryMask : 0u;
-            }
-            // (a << s) | b is one v_lshl_or_b32; the compiler emitted a shift
-            // and an or for each (5 instead of 3 per u64)
-            v[r] = make_uint4(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11),
-                              lshl_or(e[4], 21, e[3]), lshl_or(e[5], 10, e[4] >> 11));
+        if constexpr (ABL == 4) {
+            // (ablation: the scattered image consumed, one read per thread
+            // into the impossible store; unread, the compiler dropped the
+            // whole scatter)
+            if ((s_sorted[tid] ^ br[0]) == 0x9E3779B9u)
+                reinterpret_cast<uint32_t *>(pos_out)[tile * kTileKeys + tid] = br[0];
+            return;
         }
-        if constexpr (ABL == 0) {
-            if constexpr (NT) {
-                // sorted tiles beyond the Infinity Cache (C5: 512 MiB): stored
-                // non-temporal, so they do not evict what pass 2 can use
-                // there (C5 build 0.419 -> 0.406 ms; below it, C2's 128 MiB,
-                // pass 2 reads them from the cache: 35 us, 48 from HBM; a
-                // runtime choice in the kernel spilled 3-4 VGPRs)
+        // 4. (not deferred) the sorted tile goes out at once
+        if constexpr (!DEFER) {
 #pragma unroll
-                for (int r = 0; r < kStores; r++) nt_store16(dst + r * TB + tid, v[r]);
-            } else {
+            for (int r = 0; r < kStores; r++) pack_store(full_c, r, tile, tile_keys);
+        }
+    };
+    // The block's last tile has no next tile to go out under.
+    auto write_out = [&](auto full_c, size_t tile) {
+        if constexpr (DEFER && kPacks) {
+            const int tile_keys = (int)min((size_t)kTileKeys, ks.n - tile * kTileKeys);
 #pragma unroll
-                for (int r = 0; r < kStores; r++) dst[r * TB + tid] = v[r];
-            }
-        } else {
-            // keep the packing: a store only when an impossible value shows
-#pragma unroll
-            for (int r = 0; r < kStores; r++)
-                if (v[r].x == 0xFFFFFFFFu && v[r].y == 0xFFFFFFFFu) dst[r * TB + tid] = v[r];
+            for (int r = 0; r < kStores; r++) pack_store(full_c, r, tile, tile_keys);
         }
     };
 
     // Full tiles in the loop; the short last tile (index ntiles - 1, always
-    // in a block's final round) after it, so the loop sees only FULL.
+    // in a block's final round) after it, so the loop sees only FULL.  With
+    // DEFER the block's first tile is peeled off: it carries no write-out,
+    // and a test of the round inside the loop kept both bodies' addresses
+    // live across it (20 spilled VGPRs).
     const size_t nfull = ks.n / kTileKeys;
     size_t tile = part_tile(0, ntiles);
-    if (tile < ntiles) load_tile_keys<LAYOUT, TB>(ks, tile, tid, kcur);
-    size_t round = 0;
-    for (; tile < nfull; round++) {
-        const size_t next = part_tile(round + 1, ntiles);
-        do_tile(BoolC<true>{}, tile, next);
+    if (tile >= ntiles) return;
+    load_tile_keys<LAYOUT, TB>(ks, tile, tid, kcur);
+    if constexpr (!DEFER) {
+        for (size_t round = 0; tile < nfull; round++) {
+            const size_t next = part_tile(round + 1, ntiles);
+            do_tile(BoolC<true>{}, BoolC<false>{}, tile, next, tile);
 #pragma unroll
-        for (int j = 0; j < kPartKPT; j++) kcur[j] = knext[j];
-        tile = next;
+            for (int j = 0; j < kPartKPT; j++) kcur[j] = knext[j];
+            tile = next;
+        }
+        if (tile < ntiles) do_tile(BoolC<false>{}, BoolC<false>{}, tile, ntiles, tile);
+    } else if (tile >= nfull) {  // the block's only tile is the short one
+        do_tile(BoolC<false>{}, BoolC<false>{}, tile, ntiles, tile);
+        write_out(BoolC<false>{}, tile);
+    } else {
+        size_t prev = tile;
+        {
+            const size_t next = part_tile(1, ntiles);
+            do_tile(BoolC<true>{}, BoolC<false>{}, tile, next, tile);
+#pragma unroll
+            for (int j = 0; j < kPartKPT; j++) kcur[j] = knext[j];
+            tile = next;
+        }
+        for (size_t round = 1; tile < nfull; round++) {
+            const size_t next = part_tile(round + 1, ntiles);
+            do_tile(BoolC<true>{}, BoolC<true>{}, tile, next, prev);
+#pragma unroll
+            for (int j = 0; j < kPartKPT; j++) kcur[j] = knext[j];
+            prev = tile;
+            tile = next;
+        }
+        if (tile < ntiles) {
+            do_tile(BoolC<false>{}, BoolC<true>{}, tile, ntiles, prev);
+            write_out(BoolC<false>{}, tile);
+        } else {
+            write_out(BoolC<true>{}, prev);
+        }
     }
-    if (tile < ntiles) do_tile(BoolC<false>{}, tile, ntiles);
 }
 
 // ---------------------------------------------------------------------------
@@ -2100,6 +2166,11 @@ void bin_launch(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace
                 uint32_t *runs, const SegMap &sm, bool cols, uint16_t *slots, hipStream_t stream) {
     constexpr int kWgs = part_bin_wgs_per_cu<TB, SLOTS, MAXB>();
     constexpr int kMinW = kWgs * TB / 256;  // waves per SIMD the registers must allow
+    // The write-out is deferred into the next tile's hash phase (k_part_bin's
+    // DEFER) where that measured faster: the 1024-thread builds (C5 0.394 ->
+    // 0.385 ms).  With the slot plane (C3's probe) it is level, and on 512
+    // threads at three workgroups per CU (C2) slower, 54.7 -> 56.0 us.
+    constexpr bool kDefer = TB >= 1024 && !SLOTS;
     const size_t g = (size_t)device_cu_count() * kWgs;
     const unsigned grid = (unsigned)(ws.ntiles < g ? ws.ntiles : g);
     if constexpr (!SLOTS && TB >= 1024 && MAXB == 1023) {
@@ -2107,19 +2178,19 @@ void bin_launch(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace
         // non-temporal (k_part_bin's NT)
         if (ws.ntiles * (uint64_t)(TB * kPartKPT) * 8 > kInfinityCacheBytes) {
             if (cols)
-                k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW, 0, true><<<grid, TB, 0, stream>>>(
-                    ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
+                k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW, 0, true, kDefer>
+                    <<<grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
             else
-                k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW, 0, true><<<grid, TB, 0, stream>>>(
-                    ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
+                k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW, 0, true, kDefer>
+                    <<<grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
             return;
         }
     }
     if (cols)
-        k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW><<<grid, TB, 0, stream>>>(
+        k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW, 0, false, kDefer><<<grid, TB, 0, stream>>>(
             ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
     else
-        k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW><<<grid, TB, 0, stream>>>(
+        k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW, 0, false, kDefer><<<grid, TB, 0, stream>>>(
             ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
 }
 

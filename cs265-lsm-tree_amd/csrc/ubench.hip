@@ -383,19 +383,24 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
         // 5100 + ABL: the product's C2 pass 1 (plan_build's one-member
         // ladder, 4096-key tiles, three workgroups per CU) cut after a
         // stage (k_part_bin's ABL): the ablation ladder of tools/ubench.py p1abl
-#define UB_ABL(A)                                                                                 \
-    case 5100 + A: {                                                                             \
+        // + 20: the tile's write-out deferred into the next tile's hash
+        // phase (k_part_bin's DEFER, the 1024-thread builds' form) instead
+        // of after its own scatter (5100, the product's form at C2)
+#define UB_ABL(A, D)                                                                              \
+    case 5100 + 20 * D + A: {                                                                    \
         SegMap sm{};                                                                             \
         if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 ||           \
             ws.nbins > 511 || !runs_as_columns(ws))                                              \
             return -22;                                                                          \
         const unsigned g = (unsigned)std::min<size_t>(ws.ntiles, (size_t)device_cu_count() * 3); \
-        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, 6, A>                       \
+        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, 6, A, false, D != 0>     \
             <<<g, 512, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);           \
         e = hipGetLastError();                                                                   \
         break;                                                                                   \
     }
-        UB_ABL(0) UB_ABL(1) UB_ABL(2) UB_ABL(3) UB_ABL(4) UB_ABL(5)
+        UB_ABL(0, 0) UB_ABL(1, 0) UB_ABL(2, 0) UB_ABL(3, 0) UB_ABL(4, 0) UB_ABL(5, 0)
+        // (stages 1-4 write no tile out: the same with and without DEFER)
+        UB_ABL(0, 1) UB_ABL(5, 1)
 #undef UB_ABL
         default: return -22;
     }

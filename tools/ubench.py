@@ -176,24 +176,30 @@ def p2_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
 
 
 def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50):
-    """C2's pass 1 cut after each stage (ubench_part 5100 + ABL, k_part_bin's
-    ABL): 1 hash + bin/entry, 2 + rank atomics, 3 + scan and run table,
-    4 + scatter, 5 + packing (no tile stores), 0 = the whole pass.  Variant
-    5100 must give the product's bitmap through the product's pass 2;
-    interleaved rounds."""
+    """C2's pass 1 cut after each stage (ubench_part 5100 + 20 * DEFER + ABL,
+    k_part_bin's ABL): 1 hash + bin/entry, 2 + rank atomics, 3 + scan and run
+    table, 4 + scatter (the image read once), 5 + packing (no tile stores),
+    0 = the whole pass.  Stages 1-4 write no tile out, so they are the same
+    for every DEFER; stages 5 and 0 are priced with the write-out after the
+    tile's own scatter (DEFER 0: 5105, 5100) and deferred into the next
+    tile's hash phase (5125, 5120).  5100 and 5120 must
+    give the product's bitmap through the product's pass 2; interleaved
+    rounds."""
     run, words, geo = _part_setup(n, bpe)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
     ref = words.clone()
-    words.zero_()
-    assert run(5100) == 0 and run(1) == 0
-    torch.cuda.synchronize()
-    print(json.dumps({"check": "ablation variant 5100 bitmap == product", "ok": bool(torch.equal(ref, words))}),
-          flush=True)
+    for v in (5100, 5120):
+        words.zero_()
+        assert run(v) == 0 and run(1) == 0
+        torch.cuda.synchronize()
+        print(json.dumps({"check": f"ablation variant {v} bitmap == product",
+                          "ok": bool(torch.equal(ref, words))}), flush=True)
     names = {5101: "hash + bin/entry", 5102: "+ rank atomics", 5103: "+ scan, run table",
-             5105: "+ scatter + packing (no stores)", 5100: "whole pass 1", 0: "product pass 1"}
-    # (ABL 4, the scatter without the packing, is left out: nothing reads the
-    # scattered image, so the compiler drops the scatter and the entries)
+             5104: "+ scatter", 5105: "+ packing after the scatter (no stores)",
+             5100: "whole pass 1, write-out after the scatter",
+             5125: "+ packing deferred (no stores)", 5120: "whole pass 1, write-out deferred",
+             0: "product pass 1"}
     _prewarm(run, 0)
     res = {v: [] for v in names}
     for _ in range(rounds):
