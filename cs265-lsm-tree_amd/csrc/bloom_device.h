@@ -908,19 +908,6 @@ constexpr int kApplyBlock = 1024;
 constexpr int kStageBatch = 4;
 constexpr int kApplyDepth = 2;  // lane-group loads per wave per batch
 
-// Lanes per tile for pass 2, from the average run length L = tile entries /
-// nbins: a step reads 6G entries of a tile (G lanes x one 16-B vector);
-// runs longer than a step finish in the wave-uniform tail loop.  Measured
-// (tools/ubench.py part*, G x depth sweep): G = 4 wins from runs of 8 (C4)
-// to 48 entries (C2, C5): C2 38 us vs 66 at G = 8 and 47 at G = 2.
-inline int apply_lanes_per_tile(size_t nbins, size_t tile_pos = kPartTilePos) {
-    const size_t L = tile_pos / (nbins ? nbins : 1);
-    if (L < 96) return 4;
-    if (L < 192) return 8;
-    if (L < 384) return 16;
-    return 32;
-}
-
 // MODE kApplyBuild: OR every entry into the zeroed LDS image, write the
 // segment.  kApplyProbe: the LDS image is the filter's segment; each entry's
 // bit is written as one result byte at the entry's own index in the sorted
@@ -945,8 +932,77 @@ constexpr int kApplyBuild = 0, kApplyProbe = 1, kApplyStack = 2, kApplyLadder = 
 // a << t | b << s (StackTable::lad's s, t[0], d).
 constexpr int kApplyBuildL = 4;
 
+// Lanes per tile for pass 2, from the average run length L = tile entries /
+// nbins: a step reads 6G entries of a tile (G lanes x one 16-B vector);
+// runs longer than a step finish in the wave-uniform tail loop.  Measured
+// (tools/ubench.py part*, G x depth sweep): G = 4 wins from runs of 8 (C4)
+// to 48 entries (C2, C5): C2 38 us vs 66 at G = 8 and 47 at G = 2.
+inline int apply_lanes_per_tile(size_t nbins, size_t tile_pos = kPartTilePos) {
+    const size_t L = tile_pos / (nbins ? nbins : 1);
+    if (L < 96) return 4;
+    if (L < 192) return 8;
+    if (L < 384) return 16;
+    return 32;
+}
+
+// The walk of one pass-2 launch: k_part_apply's G, CHAINS, VECS and REDIR.
+struct ApplyWalk {
+    int g;       // lanes per tile
+    int chains;  // 0: the batch walk; 1 or 2: independent lane groups, chains per group
+    int vecs;    // 16-B vectors per lane and step
+    bool redir;  // a load past the run's end goes to the group's first vector
+};
+inline bool operator==(const ApplyWalk &a, const ApplyWalk &b) {
+    return a.g == b.g && a.chains == b.chains && a.vecs == b.vecs && a.redir == b.redir;
+}
+
+// The walk pass 2 takes for a batch of ntiles tiles of tile_keys keys sorted
+// into nbins segments, by mode: every threshold of the choice, with what was
+// measured for it.  launch_apply compiles exactly the walks this returns.
+inline ApplyWalk choose_apply_walk(int mode, size_t tile_keys, size_t nbins, size_t ntiles) {
+    const ApplyWalk batch8{8, 0, 1, false};
+    // runs shorter than a group's step (4 lanes x 6 entries): loads past a
+    // run's end are redirected (k_part_apply's vload)
+    const bool short_runs = 3 * tile_keys / (nbins ? nbins : 1) < 24;
+    // entries beyond the Infinity Cache are read from HBM
+    const bool from_hbm = (uint64_t)ntiles * tile_keys * 8 > kInfinityCacheBytes;
+    // the ladder stack: batch walk at G = 8 (C3, 5 levels at 96-entry runs:
+    // 75.6 us against 84.2 for independent groups at G = 4 and 78.5 at G = 8)
+    if (mode == kApplyLadder) return batch8;
+    if (tile_keys == kSuperTileKeys) {
+        // a segment stack on super-tiles (plan_stack: 1,024-4,095 segments,
+        // runs of 12-48 entries): four lanes per tile, two vectors per lane
+        if (mode == kApplyStack) return {4, 1, 2, true};
+        // a build on super-tiles: >= kSuperMinBins segments, runs of at most
+        // 48 entries on average: independent groups of 4 lanes.  Short runs:
+        // two vectors per lane, on two interleaved chains per lane group (C4
+        // pass 2 795 -> 764 us; three chains 875, four 916,
+        // profiles/r06/c4_two_chains/)
+        if (short_runs) return {4, 2, 2, true};
+        return {4, 1, 1, false};
+    }
+    const int g = apply_lanes_per_tile(nbins, 3 * tile_keys);
+    if (mode == kApplyStack) {
+        // independent lane groups at G = 4 (C3, 5 levels: 108 -> 102 us; 4
+        // levels: equal), else the batch walk at G = 8
+        if (g > 4) return batch8;
+        return {4, 1, 1, short_runs};
+    }
+    // single probes, and every longer run: the batch walk
+    if (mode == kApplyProbe || g > 4) return {g, 0, 1, false};
+    // builds: independent lane groups (C2 pass 2 39.5 -> 34.4 us, C4 1.39 ->
+    // 1.36 ms)
+    if (short_runs) return {4, 1, 1, true};
+    // entries from HBM (C5: 512 MiB): two vectors per lane and step, so a
+    // ~48-entry run is one step with twice the loads in flight (C5 pass 2
+    // 192.5 -> 173.6 us, tools/ubench.py p2ab_c5; C2's 128 MiB equal either
+    // way, so it keeps one vector)
+    if (from_hbm) return {4, 1, 2, true};
+    return {4, 1, 1, false};
+}
+
 template <int MODE, int G, int TILE_KEYS, int BLOCK = kApplyBlock, int DEPTH = kApplyDepth,
-          int WALK = 0, int NF = 0, int LK = 0>
+          int CHAINS = 0, int VECS = 1, bool REDIR = false, int NF = 0, int LK = 0>
 __global__ void __launch_bounds__(BLOCK) k_part_apply(
     const uint64_t *__restrict__ pos, const uint32_t *__restrict__ run_starts, int ntiles,
     int nbins, uint32_t seg_bits, uint64_t m, uint32_t *__restrict__ words, uint64_t nw32,
@@ -1198,7 +1254,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
         return reinterpret_cast<const uint4 *>(pos + (size_t)rt(t) * TILE_KEYS)[min(vi, kLastVec)];
     };
     // The vector a lane loads for its step at vector vi of a run ending at
-    // entry `end`, group base vector vb.  WALK 2 (short runs): a lane whose
+    // entry `end`, group base vector vb.  REDIR (short runs): a lane whose
     // vector lies past the run's end loads the group's first vector instead
     // -- a line the group reads anyway, so the wave instruction touches fewer
     // distinct lines (C4's ~10-entry runs span 2-3 of a group's 4 vectors:
@@ -1208,7 +1264,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
     // segment's run, which an XCD neighbour reads next from the same L2
     // (C2 pass 2 35.5 -> 39.5 us with the redirect, profiles/r05/redirect/).
     auto vload = [&](uint32_t vi, uint32_t vb, uint32_t end) -> uint32_t {
-        if constexpr (WALK >= 2) return 6 * vi < end ? vi : vb;
+        if constexpr (REDIR) return 6 * vi < end ? vi : vb;
         return vi;
     };
     // The six entries of vector vi of tile t; run = [r.x, r.y).
@@ -1230,11 +1286,11 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             const int s0 = (int)(6 * vi) - (int)r.x;          // entry 0's place in the run
             const int lo = max(-s0, 0), hi = min(max((int)r.y - (int)(6 * vi), 0), 6);
             const uint32_t vm = ((1u << hi) - 1u) & ~((1u << lo) - 1u);
-            // WALK 3 (super-tiles): a lane whose vector holds none of the
-            // run's entries (a redirected load past the run's end: about half
-            // of them at C4's ~20-entry runs) issues no atomics, so the
-            // segment image's banks serve only the lanes with bits to set
-            if (WALK < 1 || vm != 0) {
+            // The group walk: a lane whose vector holds none of the run's
+            // entries (a redirected load past the run's end: about half of
+            // them at C4's ~20-entry runs on super-tiles) issues no atomics,
+            // so the segment image's banks serve only the lanes with bits to set
+            if (CHAINS == 0 || vm != 0) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
                     const uint32_t d = MODE == kApplyBuildL ? e[k] : e[k] - base21;
@@ -1371,87 +1427,8 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
         }
     };
 
-    if constexpr (WALK >= 4 && WALK <= 6) {
-        // WALK 1 / 3 / 2's walks for builds (round 6: WALK 4 / 5 / 6),
-        // restated for fewer instructions per step: unrolled over two
-        // register sets (the old loops copy their carried state at the
-        // back-edge: seven moves a step), the vector and run-bound loads
-        // addressed from uniform bases by 32-bit byte offsets (the sorted
-        // tiles span < 4 GiB: the launchers check), so a step forms a load
-        // address in two instructions instead of eight 64-bit ones, and a
-        // run's end kept in vectors (the step test multiplies nothing).
-        // Lanes past the last tile hold an empty run (r = 0).  NV vectors
-        // per lane and step (WALK 5: two, for super-tiles' ~20-entry runs);
-        // REDIR (WALK 5, 6: short runs): a lane whose vector lies past the
-        // run's end loads the group's first vector instead (WALK 2's note).
-        // Not launched: WALK 4 against WALK 1 was 1 % faster in the pass-2
-        // micro-benchmark but 4 % slower in the bench (C2 35.2 -> 36.7 us,
-        // profiles/r06/rejected/walk4_bench/), WALK 5 against WALK 3 on C4's
-        // super-tiles 806 against 796 us (profiles/r06/rejected/walk5_c4/).
-        static_assert(!PROBE, "builds");
-        constexpr int NV = WALK == 5 ? 2 : 1;
-        constexpr bool REDIR = WALK >= 5;
-        constexpr int kGroupsPerWave = 64 / G;
-        const int Q = kGroupsPerWave * (BLOCK / 64);
-        constexpr uint32_t kVecShift = __builtin_ctz((unsigned)TILE_KEYS / 2);  // vectors per tile, log2
-        const char *pos_b = reinterpret_cast<const char *>(pos);
-        const char *col_b = reinterpret_cast<const char *>(run_starts + (size_t)b * ntiles);
-        auto bnd = [&](int tt) -> uint32_t {
-            return tt < ntiles ? *reinterpret_cast<const uint32_t *>(col_b + ((uint32_t)rt(tt) << 2)) : 0u;
-        };
-        auto vec = [&](uint32_t tv, uint32_t vi) -> uint4 {
-            return *reinterpret_cast<const uint4 *>(pos_b + ((tv + min(vi, kLastVec)) << 4));
-        };
-        auto tvec = [&](int t) -> uint32_t { return (uint32_t)rt(min(t, ntiles - 1)) << kVecShift; };
-        auto ceil6 = [](uint32_t x) { return (x + 5u) / 6u; };
-        struct St {
-            int t;        // walk step: tile rt(t)
-            uint32_t r;   // its run, start | end << 16 (0: none)
-            uint32_t rn;  // the run of tile t + Q
-            uint32_t vb;  // the group's first vector of this step
-            uint32_t ev;  // the run's end in vectors, ceil(end / 6)
-            uint32_t tv;  // the tile's first vector
-            uint4 v[NV];  // this lane's vectors of the step: vb + sub + G k
-        };
-        auto loads = [&](St &s) {
-#pragma unroll
-            for (int k = 0; k < NV; k++) {
-                const uint32_t vi = s.vb + sub + G * k;
-                s.v[k] = vec(s.tv, REDIR && vi >= s.ev ? s.vb : vi);
-            }
-        };
-        St A, B;
-        A.t = wave * kGroupsPerWave + tl;
-        A.r = bnd(A.t);
-        A.rn = bnd(A.t + Q);
-        A.vb = (A.r & 0xFFFFu) / 6u;
-        A.ev = ceil6(A.r >> 16);
-        A.tv = tvec(A.t);
-        loads(A);
-        // the step after c into n (its loads issued first), then c applied
-        auto step = [&](const St &c, St &n) {
-            const uint32_t vb2 = c.vb + NV * G;
-            const bool adv = vb2 >= c.ev;
-            n.t = adv ? c.t + Q : c.t;
-            n.r = adv ? c.rn : c.r;
-            n.vb = adv ? (c.rn & 0xFFFFu) / 6u : vb2;
-            n.ev = adv ? ceil6(c.rn >> 16) : c.ev;
-            n.tv = adv ? tvec(c.t + Q) : c.tv;
-            n.rn = c.rn;
-            if (adv) n.rn = bnd(c.t + 2 * Q);
-            loads(n);
-            if (c.vb < c.ev) {
-#pragma unroll
-                for (int k = 0; k < NV; k++) apply6(c.v[k], c.t, c.vb + sub + G * k, dec(c.r));
-            }
-        };
-        while (true) {
-            if (__ballot(A.t < ntiles) == 0) break;
-            step(A, B);
-            if (__ballot(B.t < ntiles) == 0) break;
-            step(B, A);
-        }
-    } else if constexpr (WALK == 1 || WALK == 2) {
+    static_assert(VECS == 1 || VECS == 2, "vectors per lane and step");
+    if constexpr (CHAINS == 1 && VECS == 1) {
         // Independent lane groups: group q (G lanes) walks tiles q, q + Q,
         // q + 2Q, ... one step (G vectors) per iteration, moving to its next
         // tile as soon as its run ends, so no group waits for the longest run
@@ -1489,22 +1466,18 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             if (t < ntiles && 6 * vb < (r >> 16)) apply6(v, t, vb + sub, dec(r));
             t = t2; r = r2; rn = rn2; vb = vb2; v = v2;
         }
-    } else if constexpr (WALK >= 7) {
-        // WALK 3 on two interleaved chains per lane group (round 6): chain c
-        // walks the group's tiles q + c Q, q + (2 + c) Q, ..., both chains'
-        // next vectors in flight together, so a lane holds four 16-B loads
-        // and two run-bound loads in flight instead of two and one (C4's
-        // entries come from HBM, not the Infinity Cache: its pass 2 waits on
-        // load latency, one (tile, segment) pair per group step).  WALK 10:
-        // WALK 1 (one vector per lane, no redirect) on two chains.
+    } else if constexpr (CHAINS == 2) {
+        // The same walk on two interleaved chains per lane group (round 6):
+        // chain c walks the group's tiles q + c Q, q + (2 + c) Q, ..., both
+        // chains' next vectors in flight together, so at two vectors per lane
+        // a lane holds four 16-B loads and two run-bound loads in flight
+        // instead of two and one (C4's entries come from HBM, not the
+        // Infinity Cache: its pass 2 waits on load latency, one (tile,
+        // segment) pair per group step).
         constexpr int kGroupsPerWave = 64 / G;
         const int Q = kGroupsPerWave * (BLOCK / 64);
-        constexpr int NC = WALK == 10 ? 2 : WALK - 5;  // WALK 7: 2 chains (launched), 8: 3, 9: 4 (slower)
-        constexpr int NV = WALK == 10 ? 1 : 2;          // vectors per lane and step
-        auto vl = [&](uint32_t vi, uint32_t vb, uint32_t end) -> uint32_t {
-            if constexpr (WALK == 10) return vi;
-            return vload(vi, vb, end);
-        };
+        constexpr int NC = CHAINS;  // chains per lane group
+        constexpr int NV = VECS;    // vectors per lane and step
         auto bnd = [&](int tt) -> uint32_t {
             return tt < ntiles ? run_starts[(size_t)b * ntiles + rt(tt)] : 0u;
         };
@@ -1519,7 +1492,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             vb[c] = (r[c] & 0xFFFFu) / 6u;
 #pragma unroll
             for (int k = 0; k < NV; k++)
-                v[c][k] = load(min(t[c], ntiles - 1), vl(vb[c] + k * G + sub, vb[c], r[c] >> 16));
+                v[c][k] = load(min(t[c], ntiles - 1), vload(vb[c] + k * G + sub, vb[c], r[c] >> 16));
         }
         auto live = [&]() {
             bool any = false;
@@ -1549,7 +1522,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             for (int c = 0; c < NC; c++)
 #pragma unroll
                 for (int k = 0; k < NV; k++)
-                    v2[c][k] = load(min(t2[c], ntiles - 1), vl(vb2[c] + k * G + sub, vb2[c], r2[c] >> 16));
+                    v2[c][k] = load(min(t2[c], ntiles - 1), vload(vb2[c] + k * G + sub, vb2[c], r2[c] >> 16));
 #pragma unroll
             for (int c = 0; c < NC; c++) {
                 if (t[c] < ntiles && 6 * vb[c] < (r[c] >> 16)) {
@@ -1564,10 +1537,10 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
                 for (int k = 0; k < NV; k++) v[c][k] = v2[c][k];
             }
         }
-    } else if constexpr (WALK == 3) {
+    } else if constexpr (CHAINS == 1 && VECS == 2) {
         // The same walk with two vectors per lane per step (vectors vb + sub
         // and vb + G + sub: a step covers 12G entries), loads past a run's
-        // end redirected as at WALK 2: runs a little longer than one G-vector
+        // end redirected (vload): runs a little longer than one G-vector
         // step (super-tiles: ~20 entries, 4-5 vectors) take one step.
         constexpr int kGroupsPerWave = 64 / G;
         const int Q = kGroupsPerWave * (BLOCK / 64);
@@ -1599,6 +1572,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             t = t2; r = r2; rn = rn2; vb = vb2; v = v2; w = w2;
         }
     } else {
+    static_assert(CHAINS == 0 && VECS == 1 && !REDIR, "the batch walk");
     uint32_t rp[DEPTH];  // this batch's bounds, packed
     if (wave < nbatch) bounds(wave, rp);
     for (int j = wave; j < nbatch; j += (BLOCK / 64)) {
@@ -2405,7 +2379,8 @@ inline void stack_stride(size_t nbins, uint32_t seg_words, size_t lds, StackTabl
 
 // Launches pass 2 (build or probe) with S/8 bytes of dynamic LDS (> 64 KiB
 // must be opted into per kernel).
-template <int MODE, int G, int TK, int DEPTH = kApplyDepth, int WALK = 0, int NF = 0, int LK = 0>
+template <int MODE, int G, int TK, int DEPTH = kApplyDepth, int CHAINS = 0, int VECS = 1,
+          bool REDIR = false, int NF = 0, int LK = 0>
 hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *words,
                           uint64_t nw32, int merge, uint8_t *res, const StackTable &st,
                           hipStream_t stream) {
@@ -2415,8 +2390,8 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     // address 0, i.e. while the kernel has no static LDS: checked once per
     // instantiation from the code object, and the launch refused otherwise.
     static const bool lds_ok = [] {
-        const void *fn =
-            reinterpret_cast<const void *>(&k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, WALK, NF, LK>);
+        const void *fn = reinterpret_cast<const void *>(
+            &k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK>);
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(kStackMaxBits / 8));
         hipFuncAttributes fa{};
@@ -2431,132 +2406,125 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     sk.keep_mask = 0;
     if (MODE == kApplyStack && NF < 8 && G == 4) stack_stride(ws.nbins, ws.seg_bits / 32, lds, sk);
     const unsigned grid = sk.seg_stride ? (unsigned)sk.seg_stride : (unsigned)ws.nbins;
-    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, WALK, NF, LK><<<grid, kApplyBlock, lds, stream>>>(
-        ws.pos, ws.run_starts, (int)ws.ntiles, (int)ws.nbins, ws.seg_bits, m, words, nw32, merge,
-        res, sk);
+    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK>
+        <<<grid, kApplyBlock, lds, stream>>>(ws.pos, ws.run_starts, (int)ws.ntiles, (int)ws.nbins,
+                                             ws.seg_bits, m, words, nw32, merge, res, sk);
     return hipGetLastError();
 }
 
 // The stacked pass 2 with the member count compiled in (straight-line member
 // reads instead of a guarded loop over up to kMaxStack), G lanes per tile.
-template <int G, int TK, int WALK = 0>
+template <int G, int TK, int CHAINS, int VECS, bool REDIR>
 hipError_t launch_stack_nf(const PartitionWorkspace &ws, uint64_t m, uint8_t *res,
                            const StackTable &st, hipStream_t stream) {
     switch (st.nf) {
-#define STACK_NF(N) \
-    case N: return launch_apply_g<kApplyStack, G, TK, kApplyDepth, WALK, N>(ws, m, nullptr, 0, 0, res, st, stream);
+#define STACK_NF(N)                                                                              \
+    case N:                                                                                      \
+        return launch_apply_g<kApplyStack, G, TK, kApplyDepth, CHAINS, VECS, REDIR, N>(ws, m, nullptr, 0, 0, \
+                                                                                       res, st, stream);
         STACK_NF(2) STACK_NF(3) STACK_NF(4) STACK_NF(5) STACK_NF(6) STACK_NF(7) STACK_NF(8)
 #undef STACK_NF
-        default: return launch_apply_g<kApplyStack, G, TK, kApplyDepth, WALK>(ws, m, nullptr, 0, 0, res, st, stream);
+        default:
+            return launch_apply_g<kApplyStack, G, TK, kApplyDepth, CHAINS, VECS, REDIR>(ws, m, nullptr, 0, 0,
+                                                                                        res, st, stream);
     }
 }
 
-// The ladder's pass 2 with the member count and the direct members (plan_ladder:
-// 1, 2, 3 or all of them) compiled in.
-template <int G, int TK, int WALK, int N, int D = kApplyDepth>
+// The ladder's pass 2 (batch walk) with the member count and the direct
+// members (plan_ladder: 1, 2, 3 or all of them) compiled in.
+template <int G, int TK, int N, int LK>
+hipError_t launch_ladder_g(const PartitionWorkspace &ws, uint64_t m, uint8_t *res,
+                           const StackTable &st, hipStream_t stream) {
+    return launch_apply_g<kApplyLadder, G, TK, kApplyDepth, 0, 1, false, N, LK>(ws, m, nullptr, 0, 0, res,
+                                                                                st, stream);
+}
+
+template <int G, int TK, int N>
 hipError_t launch_ladder_k(const PartitionWorkspace &ws, uint64_t m, uint8_t *res,
                            const StackTable &st, hipStream_t stream) {
     switch (st.lad.k) {
         case 1:
             if (st.lad.ctup)  // the packed tuple computed (LadderTable::ctup)
-                return launch_apply_g<kApplyLadder, G, TK, D, WALK, N, 0>(ws, m, nullptr, 0, 0, res, st, stream);
-            return launch_apply_g<kApplyLadder, G, TK, D, WALK, N, 1>(ws, m, nullptr, 0, 0, res, st, stream);
-        case 2: return launch_apply_g<kApplyLadder, G, TK, D, WALK, N, 2>(ws, m, nullptr, 0, 0, res, st, stream);
+                return launch_ladder_g<G, TK, N, 0>(ws, m, res, st, stream);
+            return launch_ladder_g<G, TK, N, 1>(ws, m, res, st, stream);
+        case 2: return launch_ladder_g<G, TK, N, 2>(ws, m, res, st, stream);
         case 3:
             if constexpr (N >= 3)
-                return launch_apply_g<kApplyLadder, G, TK, D, WALK, N, 3>(ws, m, nullptr, 0, 0, res, st, stream);
+                return launch_ladder_g<G, TK, N, 3>(ws, m, res, st, stream);
             else
                 return hipErrorInvalidValue;
         default:
             if (st.lad.k != (uint32_t)N) return hipErrorInvalidValue;
-            return launch_apply_g<kApplyLadder, G, TK, D, WALK, N, N>(ws, m, nullptr, 0, 0, res, st, stream);
+            return launch_ladder_g<G, TK, N, N>(ws, m, res, st, stream);
     }
 }
 
-template <int G, int TK, int WALK = 1, int D = kApplyDepth>
+template <int G, int TK>
 hipError_t launch_ladder_nf(const PartitionWorkspace &ws, uint64_t m, uint8_t *res,
                             const StackTable &st, hipStream_t stream) {
     switch (st.nf) {
-        case 2: return launch_ladder_k<G, TK, WALK, 2, D>(ws, m, res, st, stream);
-        case 3: return launch_ladder_k<G, TK, WALK, 3, D>(ws, m, res, st, stream);
-        case 4: return launch_ladder_k<G, TK, WALK, 4, D>(ws, m, res, st, stream);
-        case 5: return launch_ladder_k<G, TK, WALK, 5, D>(ws, m, res, st, stream);
-        case 6: return launch_ladder_k<G, TK, WALK, 6, D>(ws, m, res, st, stream);
-        case 7: return launch_ladder_k<G, TK, WALK, 7, D>(ws, m, res, st, stream);
-        case 8: return launch_ladder_k<G, TK, WALK, 8, D>(ws, m, res, st, stream);
+        case 2: return launch_ladder_k<G, TK, 2>(ws, m, res, st, stream);
+        case 3: return launch_ladder_k<G, TK, 3>(ws, m, res, st, stream);
+        case 4: return launch_ladder_k<G, TK, 4>(ws, m, res, st, stream);
+        case 5: return launch_ladder_k<G, TK, 5>(ws, m, res, st, stream);
+        case 6: return launch_ladder_k<G, TK, 6>(ws, m, res, st, stream);
+        case 7: return launch_ladder_k<G, TK, 7>(ws, m, res, st, stream);
+        case 8: return launch_ladder_k<G, TK, 8>(ws, m, res, st, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
+// Pass 2 of mode MODE over TK-key tiles on the walk choose_apply_walk gives.
+// Each (MODE, TK) lists the walks the choice can return for it, so the
+// library holds exactly the kernels it launches.
 template <int MODE, int TK>
 hipError_t launch_apply_tk(const PartitionWorkspace &ws, uint64_t m, uint32_t *words,
                            uint64_t nw32, int merge, uint8_t *res, const StackTable &st,
                            hipStream_t stream) {
-    if constexpr (MODE == kApplyLadder) {
-        // batch walk at G = 8 (C3, 5 levels at 96-entry runs: 75.6 us against
-        // 84.2 for independent groups at G = 4 and 78.5 at G = 8)
-        return launch_ladder_nf<8, TK, 0>(ws, m, res, st, stream);
-    } else if constexpr (MODE == kApplyStack) {
-        // independent lane groups at G = 4 (C3, 5 levels: 108 -> 102 us; 4 levels: equal)
-        if (apply_lanes_per_tile(ws.nbins, 3 * TK) <= 4) {
-            if (3 * TK / ws.nbins < 24)  // short runs: loads past a run's end redirected
-                return launch_stack_nf<4, TK, 2>(ws, m, res, st, stream);
-            return launch_stack_nf<4, TK, 1>(ws, m, res, st, stream);
-        }
-        return launch_stack_nf<8, TK>(ws, m, res, st, stream);
-    } else {
-        switch (apply_lanes_per_tile(ws.nbins, 3 * TK)) {
-            case 4:  // builds: independent lane groups (C2 pass 2 39.5 -> 34.4 us, C4 1.39 -> 1.36 ms),
-                     // runs shorter than a group's step: loads past a run's end redirected
-                if constexpr (MODE == kApplyBuild || MODE == kApplyBuildL) {
-                    if (3 * TK / ws.nbins < 24)
-                        return launch_apply_g<MODE, 4, TK, 1, 2>(ws, m, words, nw32, merge, res, st, stream);
-                    // entries beyond the Infinity Cache (C5: 512 MiB, read
-                    // from HBM): two vectors per lane and step, so a ~48-entry
-                    // run is one step with twice the loads in flight (C5 pass 2
-                    // 192.5 -> 173.6 us, tools/ubench.py p2ab_c5; C2's 128 MiB
-                    // equal either way, so it keeps WALK 1)
-                    if ((uint64_t)ws.ntiles * TK * 8 > kInfinityCacheBytes)
-                        return launch_apply_g<MODE, 4, TK, 1, 3>(ws, m, words, nw32, merge, res, st, stream);
-                    // (round 6's restated walk, WALK 4, was 1 % faster in
-                    // tools/ubench.py p2ab but slower in the bench, where pass 2
-                    // follows pass 1: C2 pass 2 35.2 -> 36.7 us, value 187.6 ->
-                    // 184.6, profiles/r06/rejected/walk4_bench/; not launched)
-                    return launch_apply_g<MODE, 4, TK, 1, 1>(ws, m, words, nw32, merge, res, st, stream);
-                } else
-                    return launch_apply_g<MODE, 4, TK>(ws, m, words, nw32, merge, res, st, stream);
-            case 8: return launch_apply_g<MODE, 8, TK>(ws, m, words, nw32, merge, res, st, stream);
-            case 16: return launch_apply_g<MODE, 16, TK>(ws, m, words, nw32, merge, res, st, stream);
-            default: return launch_apply_g<MODE, 32, TK>(ws, m, words, nw32, merge, res, st, stream);
-        }
+    constexpr bool kSuper = TK == (int)kSuperTileKeys;
+    const ApplyWalk w = choose_apply_walk(MODE, TK, ws.nbins, ws.ntiles);
+    // (a build's group walks at one load group per batch, DEPTH 1: they have no batches)
+#define APPLY_ON(G, C, V, R)                                                                       \
+    if (w == ApplyWalk{G, C, V, R}) {                                                              \
+        if constexpr (MODE == kApplyLadder)                                                        \
+            return launch_ladder_nf<G, TK>(ws, m, res, st, stream);                                \
+        else if constexpr (MODE == kApplyStack)                                                    \
+            return launch_stack_nf<G, TK, C, V, R>(ws, m, res, st, stream);                        \
+        else                                                                                       \
+            return launch_apply_g<MODE, G, TK, C ? 1 : kApplyDepth, C, V, R>(ws, m, words, nw32, merge, res, \
+                                                                             st, stream);          \
     }
+    if constexpr (MODE == kApplyLadder) {
+        APPLY_ON(8, 0, 1, false)
+    } else if constexpr (kSuper && MODE == kApplyStack) {
+        APPLY_ON(4, 1, 2, true)
+    } else if constexpr (kSuper) {
+        APPLY_ON(4, 2, 2, true) APPLY_ON(4, 1, 1, false)
+    } else if constexpr (MODE == kApplyStack) {
+        APPLY_ON(4, 1, 1, true) APPLY_ON(4, 1, 1, false) APPLY_ON(8, 0, 1, false)
+    } else if constexpr (MODE == kApplyProbe) {
+        APPLY_ON(4, 0, 1, false) APPLY_ON(8, 0, 1, false) APPLY_ON(16, 0, 1, false) APPLY_ON(32, 0, 1, false)
+    } else {
+        APPLY_ON(4, 1, 1, true) APPLY_ON(4, 1, 2, true) APPLY_ON(4, 1, 1, false)
+        APPLY_ON(8, 0, 1, false) APPLY_ON(16, 0, 1, false) APPLY_ON(32, 0, 1, false)
+    }
+#undef APPLY_ON
+    return hipErrorInvalidValue;
 }
 
 template <int MODE>
 hipError_t launch_apply(const PartitionWorkspace &ws, uint64_t m, uint32_t *words, uint64_t nw32,
                         int merge, uint8_t *res, const StackTable &st, hipStream_t stream) {
-    if constexpr (MODE == kApplyBuild) {
-        if (tile_keys_of(ws) == kSuperTileKeys) {
-            // super-tiles: >= kSuperMinBins segments, runs of at most 48
-            // entries on average: independent groups of 4 lanes
-            constexpr int TK = (int)kSuperTileKeys;
-            // short runs: two vectors per lane, on two interleaved chains per
-            // lane group (WALK 7: C4 pass 2 795 -> 764 us; three chains 875,
-            // four 916, profiles/r06/c4_two_chains/)
-            if (3 * TK / ws.nbins < 24)
-                return launch_apply_g<MODE, 4, TK, 1, 7>(ws, m, words, nw32, merge, res, st, stream);
-            return launch_apply_g<MODE, 4, TK, 1, 1>(ws, m, words, nw32, merge, res, st, stream);
-        }
-    } else if constexpr (MODE == kApplyStack) {
-        // a segment stack on super-tiles (plan_stack: 1,024-4,095 segments,
-        // runs of 12-48 entries): four lanes per tile, two vectors per lane
-        if (tile_keys_of(ws) == kSuperTileKeys) return launch_stack_nf<4, (int)kSuperTileKeys, 3>(ws, m, res, st, stream);
+    const size_t tk = tile_keys_of(ws);
+    if (tk == kSuperTileKeys) {  // plan_build's segments and plan_stack only
+        if constexpr (MODE == kApplyBuild || MODE == kApplyStack)
+            return launch_apply_tk<MODE, (int)kSuperTileKeys>(ws, m, words, nw32, merge, res, st, stream);
+        else
+            return hipErrorInvalidValue;
     }
-    return tile_keys_of(ws) == 2 * kPartTileKeys
-               ? launch_apply_tk<MODE, 2 * (int)kPartTileKeys>(ws, m, words, nw32, merge, res, st,
-                                                               stream)
-               : launch_apply_tk<MODE, (int)kPartTileKeys>(ws, m, words, nw32, merge, res, st,
-                                                           stream);
+    return tk == 2 * kPartTileKeys
+               ? launch_apply_tk<MODE, 2 * (int)kPartTileKeys>(ws, m, words, nw32, merge, res, st, stream)
+               : launch_apply_tk<MODE, (int)kPartTileKeys>(ws, m, words, nw32, merge, res, st, stream);
 }
 
 }  // namespace

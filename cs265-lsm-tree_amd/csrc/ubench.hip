@@ -5,6 +5,7 @@
 // tools/ubench.py to pick build strategies.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include <algorithm>
 #include <numeric>
@@ -283,6 +284,100 @@ extern "C" int ubench_part_geometry(size_t n, uint64_t m, uint64_t *out4) {
     return 0;
 }
 
+namespace {
+// plan_build's one-member ladder as pass 2 takes it (launch_part_apply's table)
+StackTable ladder0_table(const ModParams &mp, const PartitionWorkspace &ws) {
+    StackTable st{};
+    st.lad.s = ws.lad_s;
+    st.lad.u = ws.lad_u;
+    st.lad.d = mp.p2d;
+    st.lad.t[0] = mp.p2t;
+    st.lad.rinv = ladder0_relabel(mp, ws) ? ladder0_inv(mp) : 0u;
+    return st;
+}
+
+// The product's build geometry of n keys into m bits on a device of ncu CUs
+// (plan_build, tiles as partition_buffers sizes them); *mode: the build's
+// pass-2 mode.
+bool build_plan(size_t n, uint64_t m, int ncu, PartitionWorkspace *ws, int *mode) {
+    if (!plan_build(m, ncu, ws)) return false;
+    if (!ws->tile_keys) ws->tile_keys = choose_tile_keys(ws->nbins);  // plan_build's super-tiles kept
+    ws->ntiles = (n + ws->tile_keys - 1) / ws->tile_keys;
+    *mode = ws->lad_u ? kApplyBuildL : kApplyBuild;
+    return true;
+}
+}  // namespace
+
+// The pass-2 walk the product chooses (choose_apply_walk) on a device of
+// cu_count CUs, with no device call: for nf = 1 a build of n keys into ms[0]
+// bits, for nf > 1 a stacked probe of n keys against filters of ms[] bits
+// (plan_ladder, else plan_stack, as probe_stacks plans it).
+// out7: mode (kApply*), tile keys, segments, G, CHAINS, VECS, REDIR.
+extern "C" int ubench_walk_choice(size_t n, int nf, const uint64_t *ms, int cu_count, int *out7) {
+    PartitionWorkspace ws{};
+    int mode = 0;
+    if (nf == 1) {
+        if (!build_plan(n, ms[0], cu_count, &ws, &mode)) return -34;
+    } else {
+        StackTable st{};
+        uint64_t mmax = 0, g = 0, mmin = ~0ull;
+        for (int j = 0; j < nf; j++) {
+            mmax = std::max(mmax, ms[j]);
+            mmin = std::min(mmin, ms[j]);
+            g = std::gcd(g, ms[j]);
+        }
+        const bool ladder = plan_ladder(ms, nf, cu_count, &st, &ws);
+        if (!ladder && !plan_stack(mmax, g, mmin, nf, cu_count, &ws)) return -34;
+        if (!ws.tile_keys) ws.tile_keys = choose_tile_keys(ws.nbins);
+        ws.ntiles = (n + ws.tile_keys - 1) / ws.tile_keys;
+        mode = ladder ? kApplyLadder : kApplyStack;
+    }
+    const ApplyWalk w = choose_apply_walk(mode, ws.tile_keys, ws.nbins, ws.ntiles);
+    const int out[7] = {mode, (int)ws.tile_keys, (int)ws.nbins, w.g, w.chains, w.vecs, (int)w.redir};
+    std::copy(out, out + 7, out7);
+    return 0;
+}
+
+// The product's pass 1, then pass 2 on a forced group walk (CHAINS, VECS,
+// REDIR) at G = 4, in the geometry's own mode and tile size: the four group
+// walks are right at any run length, only their speed differs
+// (tests/test_gpu_pass2_walks.py).  Buffers as for ubench_part.
+extern "C" int ubench_part_walk(int chains, int vecs, int redir, const void *keys, size_t n,
+                                uint64_t m, uint64_t *pos, uint32_t *runs, uint32_t *words,
+                                void *stream, size_t pos_cap, size_t runs_cap) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const KeySpan ks{reinterpret_cast<const char *>(keys), n, 4, KEYS_PACKED};
+    const ModParams mp = make_mod_params(m);
+    PartitionWorkspace ws{};
+    int mode = 0;
+    if (n == 0) return -22;
+    if (!build_plan(n, m, device_cu_count(), &ws, &mode)) return -34;
+    if (ws.ntiles * ws.tile_keys > pos_cap || 2 * ws.ntiles * (ws.nbins + 1) > runs_cap) return -28;
+    ws.pos = pos;
+    ws.run_rows = runs;
+    ws.run_starts = runs + ws.ntiles * (ws.nbins + 1);
+    hipError_t e = launch_part_bin(ks, mp, ws, s);
+    if (e != hipSuccess) {
+        fprintf(stderr, "ubench_part_walk: pass 1: %s\n", hipGetErrorString(e));
+        return -5;
+    }
+    const StackTable st = mode == kApplyBuildL ? ladder0_table(mp, ws) : StackTable{};
+    const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
+    const ApplyWalk w{4, chains, vecs, redir != 0};
+    e = hipErrorInvalidValue;  // no such walk
+#define UB_ON(MODE, TK, C, V, R)                                                                  \
+    if (mode == MODE && ws.tile_keys == TK && w == ApplyWalk{4, C, V, R})                         \
+        e = launch_apply_g<MODE, 4, TK, 1, C, V, R>(ws, mp.m, words, nw32, 0, nullptr, st, s);
+#define UB_WALKS(MODE, TK) \
+    UB_ON(MODE, TK, 1, 1, false) UB_ON(MODE, TK, 1, 1, true) UB_ON(MODE, TK, 1, 2, true) UB_ON(MODE, TK, 2, 2, true)
+    UB_WALKS(kApplyBuildL, 4096) UB_WALKS(kApplyBuildL, 8192)
+    UB_WALKS(kApplyBuild, 4096) UB_WALKS(kApplyBuild, 8192) UB_WALKS(kApplyBuild, 16384)
+#undef UB_WALKS
+#undef UB_ON
+    if (e != hipSuccess) fprintf(stderr, "ubench_part_walk: pass 2: %s\n", hipGetErrorString(e));
+    return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -22 : -5;
+}
+
 // Phases of the product's partition build (tools/ubench.py part, p1ab):
 // 0 = pass 1 as the product launches it, 1 = pass 2 as the product launches
 // it over variant 0's output; 5001 / 5003 = pass-1 shapes (MINW waves per
@@ -325,59 +420,38 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
     }
         UB_P2(5001, 512, 511, 4, 2) UB_P2(5003, 512, 511, 6, 3)
 #undef UB_P2
-        // 2500 / 2503: pass 2 of a super-tile build (C4) on the round-6
-        // walk with two vectors per lane (WALK 5) / the product's WALK 3
-        case 2500: case 2503: case 2523: case 2522: case 2507: case 2508: case 2509: case 2511: {
-            // 2523 / 2522: WALK 3 at G = 2 lanes per tile (24 entries a step
-            // for C4's ~20-entry runs) / WALK 2 (one vector) at G = 4
+        // Pass 2 of a super-tile build (C4) over variant 0's output, by
+        // k_part_apply's (G, CHAINS, VECS, REDIR): 2503 (4, 1, 2, redirected),
+        // 2507 the product's (4, 2, 2, redirected), 2522 (4, 1, 1,
+        // redirected), 2523 two lanes per tile (24 entries a step for C4's
+        // ~20-entry runs) at (2, 1, 2, redirected)
+        case 2503: case 2507: case 2522: case 2523: {
             if (ws.lad_u || tile_keys_of(ws) != kSuperTileKeys) return -22;
             const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
             constexpr int TK = (int)kSuperTileKeys;
-            if (variant == 2500)
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 5>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2503)
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 3>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2507)
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 7>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2508)
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 8>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2509)
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 9>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2523)
-                e = launch_apply_g<kApplyBuild, 2, TK, 1, 3>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else if (variant == 2511)  // two chains of one redirected vector per lane
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 11>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
-            else
-                e = launch_apply_g<kApplyBuild, 4, TK, 1, 2>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
+#define UB_WALK(V, G, C, NV, R)                                                                   \
+    if (variant == V)                                                                             \
+        e = launch_apply_g<kApplyBuild, G, TK, 1, C, NV, R>(ws, mp.m, words, nw32, 0, nullptr, StackTable{}, s);
+            UB_WALK(2503, 4, 1, 2, true) UB_WALK(2507, 4, 2, 2, true) UB_WALK(2522, 4, 1, 1, true)
+            UB_WALK(2523, 2, 1, 2, true)
+#undef UB_WALK
             break;
         }
-        // 2400 / 2401: pass 2 of plan_build's one-member ladder (C2, C5) on
-        // the round-6 build walk (WALK 4) / the product's WALK 1, over
-        // variant 0's output
-        case 2400: case 2401: case 2410: case 2413: case 2417: {
+        // Pass 2 of plan_build's one-member ladder (C2, C5) over variant 0's
+        // output at G = 4: 2401 the product's C2 walk (1, 1, plain), 2413 the
+        // product's C5 walk (1, 2, redirected), 2417 that on two chains
+        case 2401: case 2413: case 2417: {
             if (!ws.lad_u || ws.lad_hb != 0 || !mp.p2) return -22;
-            StackTable st{};
-            st.lad.s = ws.lad_s;
-            st.lad.u = ws.lad_u;
-            st.lad.d = mp.p2d;
-            st.lad.t[0] = mp.p2t;
-            st.lad.rinv = ladder0_relabel(mp, ws) ? ladder0_inv(mp) : 0u;
+            const StackTable st = ladder0_table(mp, ws);
             const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
             const size_t tk = tile_keys_of(ws);
-            if (tk == 4096)
-                e = variant == 2400 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, 4>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2410 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, 10>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2413 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, 3>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2417 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, 7>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                                    : launch_apply_g<kApplyBuildL, 4, 4096, 1, 1>(ws, mp.m, words, nw32, 0, nullptr, st, s);
-            else if (tk == 8192)
-                e = variant == 2400 ? launch_apply_g<kApplyBuildL, 4, 8192, 1, 4>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2410 ? launch_apply_g<kApplyBuildL, 4, 8192, 1, 10>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2413 ? launch_apply_g<kApplyBuildL, 4, 8192, 1, 3>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                  : variant == 2417 ? launch_apply_g<kApplyBuildL, 4, 8192, 1, 7>(ws, mp.m, words, nw32, 0, nullptr, st, s)
-                                    : launch_apply_g<kApplyBuildL, 4, 8192, 1, 1>(ws, mp.m, words, nw32, 0, nullptr, st, s);
-            else
-                return -22;
+            if (tk != 4096 && tk != 8192) return -22;
+#define UB_WALK(V, C, NV, R)                                                                      \
+    if (variant == V)                                                                             \
+        e = tk == 4096 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, C, NV, R>(ws, mp.m, words, nw32, 0, nullptr, st, s) \
+                       : launch_apply_g<kApplyBuildL, 4, 8192, 1, C, NV, R>(ws, mp.m, words, nw32, 0, nullptr, st, s);
+            UB_WALK(2401, 1, 1, false) UB_WALK(2413, 1, 2, true) UB_WALK(2417, 2, 2, true)
+#undef UB_WALK
             break;
         }
         // 5100 + ABL: the product's C2 pass 1 (plan_build's one-member
@@ -468,9 +542,9 @@ extern "C" int ubench_stack(int variant, const void *keys, size_t n, int nf, con
 }
 
 // Ladder stack (plan_ladder) on the product kernels, tile_keys 4096 or 8192:
-// 0 the whole probe, 1 pass 1, 2 pass 2 (product walk), 5 combine,
-// 20 + G pass 2 at G lanes per tile (independent groups), 30 + G batch walk,
-// 41 / 44 batch walk G = 8 at one / four load groups per wave.
+// 0 the whole probe, 1 pass 1, 2 pass 2 (product walk), 5 combine, 11 / 12
+// pass 1 without the slot stores / without slot and sorted-tile stores;
+// 100 + v: variant v on the table planner.
 extern "C" int ubench_ladder(int variant, int tile_keys, const void *keys, size_t n, int nf,
                              const uint64_t *ms, void *const *words, uint64_t *pos,
                              uint32_t *runs, uint8_t *res, uint16_t *slots, uint64_t *out,

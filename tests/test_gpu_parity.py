@@ -595,7 +595,8 @@ def test_partition_merge_then_clear_rebuild(coracle, m):
 @pytest.mark.parametrize("m", [671_088_640, 360_000_007])
 def test_hbm_resident_pass2_ragged(coracle, m):
     """Builds whose sorted entries exceed the Infinity Cache (> 256 MiB, more
-    than 33.5M keys) walk pass 2 with two vectors per lane (WALK 3): a ragged
+    than 33.5M keys) walk pass 2 on one chain of two redirected vectors per lane
+    (k_part_apply's CHAINS 1, VECS 2, REDIR): a ragged
     batch (a short last tile) on C5's ladder geometry (5 << 27) and on a
     general m (segments), against the oracle."""
     n = 33_554_432 + 3 * 8192 + 777

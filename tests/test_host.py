@@ -292,3 +292,53 @@ def test_planner_magic_bound_implies_exact(shift):
         got = (x * np.uint64(M)) >> np.uint64(32)
         want = x // np.uint64(2 * g) if shift == 31 else x // np.uint64(g)
         assert np.array_equal(got, want), g
+
+
+# Pass 2's walk per geometry (bloom_device.h choose_apply_walk) on a 256-CU
+# device, through the micro-benchmark library's ubench_walk_choice (no device
+# call).  Rows: (n keys, filter sizes: one = a build, several = a stacked
+# probe) -> (mode, tile keys, segments, G, CHAINS, VECS, REDIR).  C2 and C5
+# are the kernels recorded in profiles/pass1_overlap/kernel_stats_c2_A.csv and
+# kernel_stats_c5_A.csv; the others were read by hand off the planners and the
+# launchers as they stood before the choice became one function.
+BUILD, PROBE, STACK, LADDER, BUILD_L = 0, 1, 2, 3, 4
+WALK_ROWS = [
+    # C2, C5 run, C4
+    (16_777_216, [167_772_160], (BUILD_L, 4096, 256, 4, 1, 1, 0)),
+    (67_108_864, [671_088_640], (BUILD_L, 8192, 512, 4, 1, 2, 1)),
+    (268_435_456, [3 << 30], (BUILD, 16_384, 2458, 4, 2, 2, 1)),
+    # the f = 10 tree: level 2's build (505 segments of 8192-key tiles), the
+    # three-level stack on super-tiles (1,250 segments), two levels (320)
+    (16_777_216, [512_000_000], (BUILD, 8192, 505, 4, 1, 1, 0)),
+    (16_777_216, [512_000_000, 51_200_000, 5_120_000], (STACK, 16_384, 1250, 4, 1, 2, 1)),
+    (16_777_216, [51_200_000, 5_120_000], (STACK, 8192, 320, 4, 1, 1, 0)),
+    # C3's five-level ladder: the batch walk at G = 8
+    (16_777_216, [655_360 * 4 ** i for i in range(4, -1, -1)], (LADDER, 8192, 256, 8, 0, 1, 0)),
+    # segment builds with runs of 96 / 192 / 384 entries and more: batch walk, G = 8 / 16 / 32
+    (100_000, [100_000], (BUILD, 4096, 98, 8, 0, 1, 0)),
+    (100_000, [50_000], (BUILD, 4096, 49, 16, 0, 1, 0)),
+    (100_000, [20_000], (BUILD, 4096, 20, 32, 0, 1, 0)),
+    # runs of 24 entries against 23: super-tile builds on 2,048 and 2,049
+    # segments; 7-entry runs on 8192-key tiles (m = 2^32: 3,277 segments);
+    # 12-entry runs on the one-member ladder 5 << 29 (2,048 bins)
+    (1_000_000, [2_684_354_559], (BUILD, 16_384, 2048, 4, 1, 1, 0)),
+    (1_000_000, [2_684_354_561], (BUILD, 16_384, 2049, 4, 2, 2, 1)),
+    (1_000_000, [2**32], (BUILD, 8192, 3277, 4, 1, 1, 1)),
+    (1_000_000, [5 << 29], (BUILD_L, 8192, 2048, 4, 1, 1, 1)),
+    # sorted entries of exactly the Infinity Cache's 256 MiB (4,096 tiles of
+    # 8192 keys) against one tile more, on C5's geometry
+    (33_554_432, [671_088_640], (BUILD_L, 8192, 512, 4, 1, 1, 0)),
+    (33_554_433, [671_088_640], (BUILD_L, 8192, 512, 4, 1, 2, 1)),
+]
+
+
+@pytest.mark.parametrize("n,ms,want", WALK_ROWS)
+def test_pass2_walk_choice(n, ms, want):
+    bh.lib()  # torch's HIP runtime first (bloomhip._lib): one runtime per process
+    ub = ctypes.CDLL(os.path.join(os.path.dirname(bh.LIB_PATH), "libbloomhip_ubench.so"))
+    ub.ubench_walk_choice.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                      ctypes.c_void_p]
+    sizes = np.array(ms, dtype=np.uint64)
+    out = np.zeros(7, dtype=np.int32)
+    assert ub.ubench_walk_choice(n, len(ms), sizes.ctypes.data, 256, out.ctypes.data) == 0
+    assert tuple(int(x) for x in out) == want

@@ -90,7 +90,7 @@ def _prewarm(run, v, secs=0.5):
 
 def part_phases(n=16_777_216, bpe=10.0, reps=50):
     """The product's partition build by pass (pass 2 timed over pass 1's
-    output), and pass 2 at other lane counts / walks, two rounds."""
+    output) on plan_build's geometry and on plan_segments', two rounds."""
     run, words, geo = _part_setup(n, bpe)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
@@ -147,9 +147,15 @@ def p1_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
 
 
 def p2_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
-    """Interleaved A/B of pass-2 variants (ubench_part 2xxx / 3xxx) against
-    the product's pass 2 (1), all over the product's pass-1 output; each
-    variant's bitmap must equal the product's."""
+    """Interleaved A/B of pass-2 variants against the product's pass 2 (1),
+    all over the product's pass-1 output; each variant's bitmap must equal
+    the product's.  The variants are ubench_part's walks at G = 4 by
+    k_part_apply's (CHAINS, VECS, REDIR).  On plan_build's one-member ladder
+    (C2, C5): 2401 (1, 1, plain), 2413 (1, 2, redirected), 2417 (2, 2,
+    redirected).  On super-tiles (C4): 2522 (1, 1, redirected), 2503 (1, 2,
+    redirected), 2507 (2, 2, redirected), 2523 (1, 2, redirected) at two
+    lanes per tile.  With no applicable variant it times the product's
+    pass 2 alone (UBENCH_LIB picks the library: an A/B of two builds)."""
     run, words, geo = _part_setup(n, bpe)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
@@ -549,7 +555,7 @@ def main():
         vs = [int(v) for v in os.environ.get("UB_VARIANTS", "5001,5003").split(",")]
         return p1_ab(vs)
     if len(sys.argv) > 1 and sys.argv[1].startswith("p2ab"):
-        vs = [int(v) for v in os.environ.get("UB_VARIANTS", "2041").split(",")]
+        vs = [int(v) for v in os.environ.get("UB_VARIANTS", "").split(",") if v]
         size = {"p2ab": (16_777_216, 10.0, 50), "p2ab_c5": (67_108_864, 10.0, 20),
                 "p2ab_c4": (268_435_456, 12.0, 5)}[sys.argv[1]]
         return p2_ab(vs, *size)
