@@ -14,6 +14,7 @@
 
 #include <algorithm>
 #include <numeric>
+#include <type_traits>
 
 #include "bloom_kernels.h"
 
@@ -112,6 +113,18 @@ template <bool B>
 struct BoolC {
     static constexpr bool value = B;
 };
+
+// The sorted tiles' format: three 21-bit entries in one u64 (bits 0-20,
+// 21-41, 42-62), as its two words, and six in one 16-B vector.
+// (a << s) | b is one v_lshl_or_b32; the compiler emitted a shift
+// and an or for each (5 instead of 3 per u64)
+__device__ __forceinline__ uint2 pack_entries3(uint32_t e0, uint32_t e1, uint32_t e2) {
+    return make_uint2(lshl_or(e1, 21, e0), lshl_or(e2, 10, e1 >> 11));
+}
+__device__ __forceinline__ uint4 pack_entries6(const uint32_t (&e)[6]) {
+    return make_uint4(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11),
+                      lshl_or(e[4], 21, e[3]), lshl_or(e[5], 10, e[4] >> 11));
+}
 
 // The keys of thread tid in a pass-1 tile: the kPartKPT consecutive keys
 // tile0 + kPartKPT * tid + j, so a whole tile is read as 16-B vectors (two per
@@ -323,10 +336,7 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
 #pragma unroll
             for (int q = 0; q < 6; q++) e[q] = 6 * (r * TB + tid) + q < 3 * tile_keys ? e[q] & kEntryMask : 0u;
         }
-        // (a << s) | b is one v_lshl_or_b32; the compiler emitted a shift
-        // and an or for each (5 instead of 3 per u64)
-        const uint4 v = make_uint4(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11),
-                                   lshl_or(e[4], 21, e[3]), lshl_or(e[5], 10, e[4] >> 11));
+        const uint4 v = pack_entries6(e);
         if constexpr (ABL == 0) {
             // NT: sorted tiles beyond the Infinity Cache (C5: 512 MiB) are
             // stored non-temporal, so they do not evict what pass 2 can use
@@ -700,7 +710,7 @@ __global__ void __launch_bounds__(kSuperBlock, 4) k_part_bin2(KeySpan ks, ModPar
                     brA[q] = 0;
                 }
             }
-            stash[j * TB + tid] = make_uint2(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11));
+            stash[j * TB + tid] = pack_entries3(e[0], e[1], e[2]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // 2. B: the same, the key's entries kept packed (two registers for
@@ -721,8 +731,9 @@ __global__ void __launch_bounds__(kSuperBlock, 4) k_part_bin2(KeySpan ks, ModPar
                     brB[q] = 0;
                 }
             }
-            eB[2 * j] = lshl_or(e[1], 21, e[0]);
-            eB[2 * j + 1] = lshl_or(e[2], 10, e[1] >> 11);
+            const uint2 pk = pack_entries3(e[0], e[1], e[2]);
+            eB[2 * j] = pk.x;
+            eB[2 * j + 1] = pk.y;
             __builtin_amdgcn_sched_barrier(0);
         }
         lds_barrier();
@@ -862,9 +873,7 @@ __global__ void __launch_bounds__(kSuperBlock, 4) k_part_bin2(KeySpan ks, ModPar
                 }
                 // (plain stores: non-temporal ones, as k_part_bin's at C5, made
                 // C4's pass 1 slower, 1.299 -> 1.317 ms, more than pass 2 gained)
-                dst[ph * kVecs + r * TB + tid] =
-                    make_uint4(lshl_or(e[1], 21, e[0]), lshl_or(e[2], 10, e[1] >> 11),
-                               lshl_or(e[4], 21, e[3]), lshl_or(e[5], 10, e[4] >> 11));
+                dst[ph * kVecs + r * TB + tid] = pack_entries6(e);
             }
             if (ph == 0) lds_barrier();  // phase 0's image is read before phase 1 writes
         }
@@ -2095,20 +2104,32 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8)))
 // Exported by the kernel translation units (one instantiation family each).
 hipError_t launch_runs_transpose(const PartitionWorkspace &ws, hipStream_t stream);  // bloom_kernels.hip
 bool runs_as_columns(const PartitionWorkspace &ws);                                  // bloom_kernels.hip
-// pass 1: build / probe (slots) at 512 or 1024 threads (bloom_pass1_*.hip)
-hipError_t launch_bin_build512(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                               hipStream_t stream);
-hipError_t launch_bin_build1024(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                                hipStream_t stream);
-hipError_t launch_bin_probe512(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                               uint16_t *slots, hipStream_t stream);
-// pass 1 of a build on super-tiles (bloom_pass1_super.hip)
-hipError_t launch_bin_super(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                            hipStream_t stream);
-hipError_t launch_bin_super_probe(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                                  uint16_t *slots, hipStream_t stream);  // bloom_pass1_super_probe.hip
-hipError_t launch_bin_probe1024(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                                uint16_t *slots, hipStream_t stream);
+
+// Everything one pass-1 launch is compiled and launched with, as
+// choose_pass1_kernel returns it (template parameter of k_part_bin /
+// k_part_bin2 in capitals).
+struct Pass1Kernel {
+    bool super;      // k_part_bin2 on super-tiles, else k_part_bin
+    int threads;     // TB: 512 (4096-key tiles) or 1024 (8192-key tiles, super-tiles)
+    int layout;      // LAYOUT: KEYS_PACKED / KEYS_ENTRY (16-B aligned base only) / KEYS_STRIDED
+    bool slots;      // SLOTS: a probe, with the slot plane
+    bool cols;       // COLS: runs straight into the segment-major table, else rows + transpose
+    int mk;          // MK: the reduction kind, kMod*
+    int maxb;        // MAXB: histogram capacity
+    int wgs_per_cu;  // resident workgroups per CU: MINW = pass1_min_waves(threads, wgs_per_cu)
+    bool nt;         // NT: the sorted tiles stored non-temporal
+    bool defer;      // DEFER: a tile's write-out inside the next tile's hash phase
+    unsigned grid;   // persistent workgroups
+};
+// pass 1: the unit of each family launches the kernel p names; false when it
+// holds no such kernel.  Build / probe (slots) at 512 or 1024 threads
+// (bloom_pass1_*.hip), a build / probe on super-tiles (bloom_pass1_super*.hip).
+using Pass1Launch = bool(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                         const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                         hipStream_t stream);
+// (six function declarations, one signature: each unit defines its own)
+Pass1Launch launch_bin_build512, launch_bin_build1024, launch_bin_probe512, launch_bin_probe1024,
+    launch_bin_super, launch_bin_super_probe;
 // pass 2 of the probes (bloom_probe.hip, bloom_probe_ladder.hip) and the combine
 hipError_t launch_apply_stack(const PartitionWorkspace &ws, uint64_t m, uint8_t *res,
                               const StackTable &st, hipStream_t stream);
@@ -2120,68 +2141,57 @@ hipError_t launch_combine(const PartitionWorkspace &ws, const uint8_t *res, cons
 
 namespace {
 
+// The most segments a family's histogram and rank fields hold.
+constexpr int pass1_max_bins(bool super, int threads) {
+    return super ? (int)kSuperMaxBins : threads >= 1024 ? (int)kPartMaxBinsBig : (int)kPartMaxBins;
+}
+
+// The reduction kinds a family takes: the one-member ladder is a build's;
+// super-tiles sort segments of m < 2^32.
+constexpr bool pass1_takes_kind(bool super, bool slots, int mk) {
+    if (super) return mk == kModP2 || mk == kModFast;
+    return mk >= 0 && !(slots && (mk == kModLadder0 || mk == kModLadder0R));
+}
+
 // One pass-1 launch: MAXB is the histogram capacity the kernel is compiled
 // for (its scan loop and registers follow it, so a small capacity is cheaper:
 // C2's 256 segments at MAXB 511 run pass 1 in 74.5 us against 87 at 4096,
 // tools/ubench.py part with UB_P1).  Only the packed / entry_t fast paths get
 // the small capacities; strided keys and m >= 2^32 use the largest.
+constexpr int pass1_capacity(int threads, int layout, int mk, size_t nbins) {
+    const int cap = pass1_max_bins(false, threads);
+    if (layout == KEYS_STRIDED || mk == kModWide) return cap;
+    if (threads >= 1024) return nbins <= 1023 ? 1023 : nbins <= 2047 ? 2047 : nbins <= 4095 ? 4095 : cap;
+    return nbins <= 511 ? 511 : cap;
+}
+
 // Workgroups of pass 1 resident per CU: the 4096-key build tile with a
 // histogram of <= 511 bins takes 50 KiB of LDS, so three fit a CU when the
 // registers are capped for 6 waves per SIMD (80 VGPRs, 2 spilled): C2 pass 1
 // 59.5 -> 58.1 us (tools/ubench.py p1ab, variant 5003).  Everything else:
 // two 512-thread or one 1024-thread workgroup per CU.
-template <int TB, bool SLOTS, int MAXB>
-constexpr int part_bin_wgs_per_cu() {
-    return TB >= 1024 ? 1 : (!SLOTS && MAXB > 0 && MAXB <= 511) ? 3 : 2;
+constexpr int pass1_wgs_per_cu(int threads, bool slots, int maxb) {
+    return threads >= 1024 ? 1 : (!slots && maxb > 0 && maxb <= 511) ? 3 : 2;
+}
+// waves per SIMD the registers must allow (MINW) for wgs workgroups per CU
+constexpr int pass1_min_waves(int threads, int wgs) { return wgs * threads / 256; }
+// persistent workgroups: every resident slot of the device, at most one per tile
+inline unsigned pass1_grid(size_t ntiles, int ncu, int wgs) {
+    const size_t g = (size_t)ncu * wgs;
+    return (unsigned)(ntiles < g ? ntiles : g);
 }
 
-template <int L, bool SLOTS, int TB, int MK, int MAXB>
-void bin_launch(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                uint32_t *runs, const SegMap &sm, bool cols, uint16_t *slots, hipStream_t stream) {
-    constexpr int kWgs = part_bin_wgs_per_cu<TB, SLOTS, MAXB>();
-    constexpr int kMinW = kWgs * TB / 256;  // waves per SIMD the registers must allow
-    // The write-out is deferred into the next tile's hash phase (k_part_bin's
-    // DEFER) where that measured faster: the 1024-thread builds (C5 0.394 ->
-    // 0.385 ms).  With the slot plane (C3's probe) it is level, and on 512
-    // threads at three workgroups per CU (C2) slower, 54.7 -> 56.0 us.
-    constexpr bool kDefer = TB >= 1024 && !SLOTS;
-    const size_t g = (size_t)device_cu_count() * kWgs;
-    const unsigned grid = (unsigned)(ws.ntiles < g ? ws.ntiles : g);
-    if constexpr (!SLOTS && TB >= 1024 && MAXB == 1023) {
-        // builds whose sorted tiles exceed the Infinity Cache (C5): stored
-        // non-temporal (k_part_bin's NT)
-        if (ws.ntiles * (uint64_t)(TB * kPartKPT) * 8 > kInfinityCacheBytes) {
-            if (cols)
-                k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW, 0, true, kDefer>
-                    <<<grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
-            else
-                k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW, 0, true, kDefer>
-                    <<<grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
-            return;
-        }
-    }
-    if (cols)
-        k_part_bin<L, SLOTS, true, TB, MK, MAXB, kMinW, 0, false, kDefer><<<grid, TB, 0, stream>>>(
-            ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
-    else
-        k_part_bin<L, SLOTS, false, TB, MK, MAXB, kMinW, 0, false, kDefer><<<grid, TB, 0, stream>>>(
-            ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
-}
+// The write-out is deferred into the next tile's hash phase (k_part_bin's
+// DEFER) where that measured faster: the 1024-thread builds (C5 0.394 ->
+// 0.385 ms).  With the slot plane (C3's probe) it is level, and on 512
+// threads at three workgroups per CU (C2) slower, 54.7 -> 56.0 us.
+constexpr bool pass1_defer(int threads, bool slots) { return threads >= 1024 && !slots; }
 
-template <int L, bool SLOTS, int TB, int MK>
-void bin_launch_fast(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                     uint32_t *runs, const SegMap &sm, bool cols, uint16_t *slots,
-                     hipStream_t stream) {
-    const size_t nb = ws.nbins;
-    if constexpr (TB >= 1024) {
-        if (nb <= 1023) bin_launch<L, SLOTS, TB, MK, 1023>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else if (nb <= 2047) bin_launch<L, SLOTS, TB, MK, 2047>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else if (nb <= 4095) bin_launch<L, SLOTS, TB, MK, 4095>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else bin_launch<L, SLOTS, TB, MK, (int)kPartMaxBinsBig>(ks, mp, ws, runs, sm, cols, slots, stream);
-    } else {
-        if (nb <= 511) bin_launch<L, SLOTS, TB, MK, 511>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else bin_launch<L, SLOTS, TB, MK, (int)kPartMaxBins>(ks, mp, ws, runs, sm, cols, slots, stream);
-    }
+// builds whose sorted tiles exceed the Infinity Cache (C5): stored
+// non-temporal (k_part_bin's NT); compiled for the 1024-thread builds at
+// MAXB 1023 alone
+constexpr bool pass1_may_nt(int threads, bool slots, int maxb) {
+    return !slots && threads >= 1024 && maxb == 1023;
 }
 
 // Whether pass 1 may take the p2 reduction (kModP2) for this geometry: the
@@ -2222,120 +2232,128 @@ inline int pass1_plan(const ModParams &mp, const PartitionWorkspace &ws, bool sl
     return mk;
 }
 
-template <bool SLOTS, int TB, int MK>
-void bin_launch_layout(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                       uint32_t *runs, const SegMap &sm, bool cols, uint16_t *slots,
-                       hipStream_t stream) {
-    constexpr int kCap = TB >= 1024 ? (int)kPartMaxBinsBig : (int)kPartMaxBins;
-    const bool entry16 =
-        ks.layout == KEYS_ENTRY && (reinterpret_cast<uintptr_t>(ks.base) & 15) == 0;
-    // only the packed / entry_t fast paths get the small histogram
-    // capacities; strided keys and m >= 2^32 use the largest
-    if constexpr (MK != kModWide) {
-        if (ks.layout == KEYS_PACKED)
-            bin_launch_fast<KEYS_PACKED, SLOTS, TB, MK>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else if (entry16)
-            bin_launch_fast<KEYS_ENTRY, SLOTS, TB, MK>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else
-            bin_launch<KEYS_STRIDED, SLOTS, TB, MK, kCap>(ks, mp, ws, runs, sm, cols, slots, stream);
-    } else {
-        if (ks.layout == KEYS_PACKED)
-            bin_launch<KEYS_PACKED, SLOTS, TB, MK, kCap>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else if (entry16)
-            bin_launch<KEYS_ENTRY, SLOTS, TB, MK, kCap>(ks, mp, ws, runs, sm, cols, slots, stream);
-        else
-            bin_launch<KEYS_STRIDED, SLOTS, TB, MK, kCap>(ks, mp, ws, runs, sm, cols, slots, stream);
-    }
+// The pass-1 kernel of a build (slots = false) or a probe (slots = true) of
+// batch ks on geometry ws, on a device of ncu CUs, and the segment map it is
+// launched with: every rule of the choice, each with what was measured for
+// it above.  False for a geometry pass 1 does not take.  No device call.
+inline bool choose_pass1_kernel(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
+                                bool slots, int ncu, Pass1Kernel *out, SegMap *sm) {
+    Pass1Kernel p{};
+    // Pass 1 on super-tiles (k_part_bin2): builds whose geometry plan_build gave
+    // kSuperTileKeys (segments of m < 2^32, more than kSuperMinBins of them),
+    // and plan_stack's probes on as many.  Else k_part_bin: 1024 threads for
+    // the 8192-key tile (choose_tile_keys), 512 for the 4096-key one.
+    p.super = tile_keys_of(ws) == kSuperTileKeys;
+    p.threads = p.super ? kSuperBlock : tile_keys_of(ws) == 2 * kPartTileKeys ? 1024 : 512;
+    p.slots = slots;
+    if (ws.nbins > (size_t)pass1_max_bins(p.super, p.threads)) return false;
+    p.mk = pass1_plan(mp, ws, slots, sm);
+    if (p.mk < 0 || !pass1_takes_kind(p.super, slots, p.mk)) return false;
+    // entry_t runs are read as 16-B vectors: from a 16-B aligned base only
+    p.layout = ks.layout == KEYS_PACKED ? KEYS_PACKED
+               : ks.layout == KEYS_ENTRY && (reinterpret_cast<uintptr_t>(ks.base) & 15) == 0 ? KEYS_ENTRY
+                                                                                               : KEYS_STRIDED;
+    p.maxb = p.super ? (int)kSuperMaxBins : pass1_capacity(p.threads, p.layout, p.mk, ws.nbins);
+    p.wgs_per_cu = p.super ? 1 : pass1_wgs_per_cu(p.threads, slots, p.maxb);
+    p.defer = !p.super && pass1_defer(p.threads, slots);
+    p.nt = !p.super && pass1_may_nt(p.threads, slots, p.maxb) &&
+           ws.ntiles * (uint64_t)(p.threads * kPartKPT) * 8 > kInfinityCacheBytes;
+    p.cols = runs_as_columns(ws);
+    p.grid = pass1_grid(ws.ntiles, ncu, p.wgs_per_cu);
+    *out = p;
+    return true;
 }
 
+// f(integral_constant<V>) for the V of Vs that equals v; false when none
+// does, or f's own result.
+template <int... Vs, typename F>
+bool on_value(int v, F &&f) {
+    return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
+
+// Launches the k_part_bin that p names, of the family <SLOTS, TB>.  The
+// family holds exactly the kernels choose_pass1_kernel can return for it: a
+// reduction kind the family takes, at a capacity pass1_capacity gives for
+// the layout and kind (one it maps to itself).
 template <bool SLOTS, int TB>
-hipError_t launch_bin_tb(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                         uint16_t *slots, hipStream_t stream) {
-    constexpr int kCap = TB >= 1024 ? (int)kPartMaxBinsBig : (int)kPartMaxBins;
-    if (ws.nbins > (size_t)kCap) return hipErrorInvalidValue;
-    const bool cols = runs_as_columns(ws);
-    uint32_t *runs = cols ? ws.run_starts : ws.run_rows;
-    SegMap sm{};
-    switch (pass1_plan(mp, ws, SLOTS, &sm)) {
-        case kModLadder0:
-            if constexpr (!SLOTS) {
-                bin_launch_layout<SLOTS, TB, kModLadder0>(ks, mp, ws, runs, sm, cols, slots, stream);
-                break;
-            } else {
-                return hipErrorInvalidValue;
-            }
-        case kModLadder0R:
-            if constexpr (!SLOTS) {
-                bin_launch_layout<SLOTS, TB, kModLadder0R>(ks, mp, ws, runs, sm, cols, slots, stream);
-                break;
-            } else {
-                return hipErrorInvalidValue;
-            }
-        case kModLadder: bin_launch_layout<SLOTS, TB, kModLadder>(ks, mp, ws, runs, sm, cols, slots, stream); break;
-        case kModWide: bin_launch_layout<SLOTS, TB, kModWide>(ks, mp, ws, runs, sm, cols, slots, stream); break;
-        case kModP2: bin_launch_layout<SLOTS, TB, kModP2>(ks, mp, ws, runs, sm, cols, slots, stream); break;
-        case kModFast: bin_launch_layout<SLOTS, TB, kModFast>(ks, mp, ws, runs, sm, cols, slots, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || cols) return e;
-    return launch_runs_transpose(ws, stream);
+bool launch_pass1_tile(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                       const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                       hipStream_t stream) {
+    constexpr bool kDefer = pass1_defer(TB, SLOTS);
+    if (p.super || p.threads != TB || p.slots != SLOTS || p.defer != kDefer) return false;
+    uint32_t *runs = p.cols ? ws.run_starts : ws.run_rows;
+    return on_value<kModFast, kModWide, kModP2, kModLadder, kModLadder0, kModLadder0R>(p.mk, [&](auto mk_c) {
+        return on_value<KEYS_PACKED, KEYS_ENTRY, KEYS_STRIDED>(p.layout, [&](auto layout_c) {
+            return on_value<511, 1023, 2047, 4095, pass1_max_bins(false, TB)>(p.maxb, [&](auto maxb_c) {
+                constexpr int MK = decltype(mk_c)::value, L = decltype(layout_c)::value;
+                constexpr int MAXB = decltype(maxb_c)::value;
+                constexpr bool kHeld = pass1_takes_kind(false, SLOTS, MK) && pass1_capacity(TB, L, MK, MAXB) == MAXB;
+                if constexpr (kHeld) {
+                    constexpr int kWgs = pass1_wgs_per_cu(TB, SLOTS, MAXB);
+                    constexpr int kMinW = pass1_min_waves(TB, kWgs);
+                    constexpr bool kMayNT = pass1_may_nt(TB, SLOTS, MAXB);
+                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT)) return false;
+                    auto go = [&](auto cols_c, auto nt_c) {
+                        k_part_bin<L, SLOTS, decltype(cols_c)::value, TB, MK, MAXB, kMinW, 0,
+                                   decltype(nt_c)::value, kDefer>
+                            <<<p.grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
+                    };
+                    if constexpr (kMayNT) {
+                        if (p.nt) {
+                            p.cols ? go(BoolC<true>{}, BoolC<true>{}) : go(BoolC<false>{}, BoolC<true>{});
+                            return true;
+                        }
+                    }
+                    p.cols ? go(BoolC<true>{}, BoolC<false>{}) : go(BoolC<false>{}, BoolC<false>{});
+                    return true;
+                } else {
+                    return false;
+                }
+            });
+        });
+    });
 }
 
-
-// Pass 1 on super-tiles (k_part_bin2): builds whose geometry plan_build gave
-// kSuperTileKeys (segments of m < 2^32, more than kSuperMinBins of them).
-template <int MK, bool SLOTS>
-hipError_t launch_bin_super_mk(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                               const SegMap &sm, uint16_t *slots, hipStream_t stream) {
-    const bool cols = runs_as_columns(ws);
-    uint32_t *runs = cols ? ws.run_starts : ws.run_rows;
-    const size_t g = (size_t)device_cu_count();
-    const unsigned grid = (unsigned)(ws.ntiles < g ? ws.ntiles : g);
-    const bool entry16 = ks.layout == KEYS_ENTRY && (reinterpret_cast<uintptr_t>(ks.base) & 15) == 0;
-#define SUPER_L(L, C) \
-    k_part_bin2<L, C, MK, (int)kSuperMaxBins, SLOTS><<<grid, kSuperBlock, 0, stream>>>(ks, mp, ws.pos, runs, sm, \
-                                                                                     ws.ntiles, slots)
-    if (ks.layout == KEYS_PACKED) {
-        if (cols) SUPER_L(KEYS_PACKED, true); else SUPER_L(KEYS_PACKED, false);
-    } else if (entry16) {
-        if (cols) SUPER_L(KEYS_ENTRY, true); else SUPER_L(KEYS_ENTRY, false);
-    } else {
-        if (cols) SUPER_L(KEYS_STRIDED, true); else SUPER_L(KEYS_STRIDED, false);
-    }
-#undef SUPER_L
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess || cols) return e;
-    return launch_runs_transpose(ws, stream);
-}
-
+// The same for k_part_bin2, of the family <SLOTS>: the kinds
+// pass1_takes_kind lists for super-tiles, every layout, one capacity.
 template <bool SLOTS>
-hipError_t launch_bin_super_impl(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                                 uint16_t *slots, hipStream_t stream) {
-    if (ws.nbins > kSuperMaxBins || (SLOTS && !slots)) return hipErrorInvalidValue;
-    SegMap sm{};
-    switch (pass1_plan(mp, ws, SLOTS, &sm)) {
-        case kModP2: return launch_bin_super_mk<kModP2, SLOTS>(ks, mp, ws, sm, slots, stream);
-        case kModFast: return launch_bin_super_mk<kModFast, SLOTS>(ks, mp, ws, sm, slots, stream);
-        default: return hipErrorInvalidValue;
-    }
+bool launch_pass1_super(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                        const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                        hipStream_t stream) {
+    if (!p.super || p.slots != SLOTS) return false;
+    uint32_t *runs = p.cols ? ws.run_starts : ws.run_rows;
+    return on_value<kModP2, kModFast>(p.mk, [&](auto mk_c) {
+        return on_value<KEYS_PACKED, KEYS_ENTRY, KEYS_STRIDED>(p.layout, [&](auto layout_c) {
+            auto go = [&](auto cols_c) {
+                k_part_bin2<decltype(layout_c)::value, decltype(cols_c)::value, decltype(mk_c)::value,
+                            (int)kSuperMaxBins, SLOTS>
+                    <<<p.grid, kSuperBlock, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
+            };
+            p.cols ? go(BoolC<true>{}) : go(BoolC<false>{});
+            return true;
+        });
+    });
 }
 
-// Pass 1 for a build (SLOTS = false) or a probe (SLOTS = true), then the
-// run-start transpose when the table is large: the exported instantiation
-// for the batch's tile size.
+// Pass 1 for a build (SLOTS = false) or a probe (SLOTS = true): the kernel
+// choose_pass1_kernel gives, from the unit that holds its family, then the
+// run-start transpose when the table is large.
 template <bool SLOTS>
 hipError_t launch_bin(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
                       uint16_t *slots, hipStream_t stream) {
-    const bool big = tile_keys_of(ws) == 2 * kPartTileKeys;
-    if constexpr (SLOTS) {
-        if (tile_keys_of(ws) == kSuperTileKeys) return launch_bin_super_probe(ks, mp, ws, slots, stream);
-        return big ? launch_bin_probe1024(ks, mp, ws, slots, stream)
-                   : launch_bin_probe512(ks, mp, ws, slots, stream);
-    } else {
-        if (tile_keys_of(ws) == kSuperTileKeys) return launch_bin_super(ks, mp, ws, stream);
-        return big ? launch_bin_build1024(ks, mp, ws, stream) : launch_bin_build512(ks, mp, ws, stream);
-    }
+    Pass1Kernel p{};
+    SegMap sm{};
+    if ((SLOTS && !slots) || !choose_pass1_kernel(ks, mp, ws, SLOTS, device_cu_count(), &p, &sm))
+        return hipErrorInvalidValue;
+    Pass1Launch *unit;
+    if constexpr (SLOTS)
+        unit = p.super ? launch_bin_super_probe : p.threads >= 1024 ? launch_bin_probe1024 : launch_bin_probe512;
+    else
+        unit = p.super ? launch_bin_super : p.threads >= 1024 ? launch_bin_build1024 : launch_bin_build512;
+    if (!unit(p, ks, mp, ws, sm, SLOTS ? slots : nullptr, stream)) return hipErrorInvalidValue;
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.cols) return e;
+    return launch_runs_transpose(ws, stream);
 }
 
 // The segment stack's pass 2 on persistent workgroups (round 5): member j's

@@ -5,9 +5,10 @@
 
 namespace bloomhip {
 
-hipError_t launch_bin_build512(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                               hipStream_t stream) {
-    return launch_bin_tb<false, 512>(ks, mp, ws, nullptr, stream);
+bool launch_bin_build512(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                         const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                         hipStream_t stream) {
+    return launch_pass1_tile<false, 512>(p, ks, mp, ws, sm, slots, stream);
 }
 
 }  // namespace bloomhip

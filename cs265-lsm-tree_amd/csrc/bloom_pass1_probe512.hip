@@ -5,9 +5,10 @@
 
 namespace bloomhip {
 
-hipError_t launch_bin_probe512(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                               uint16_t *slots, hipStream_t stream) {
-    return launch_bin_tb<true, 512>(ks, mp, ws, slots, stream);
+bool launch_bin_probe512(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                         const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                         hipStream_t stream) {
+    return launch_pass1_tile<true, 512>(p, ks, mp, ws, sm, slots, stream);
 }
 
 }  // namespace bloomhip

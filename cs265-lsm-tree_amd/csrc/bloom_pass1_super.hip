@@ -4,9 +4,10 @@
 
 namespace bloomhip {
 
-hipError_t launch_bin_super(const KeySpan &ks, const ModParams &mp, const PartitionWorkspace &ws,
-                            hipStream_t stream) {
-    return launch_bin_super_impl<false>(ks, mp, ws, nullptr, stream);
+bool launch_bin_super(const Pass1Kernel &p, const KeySpan &ks, const ModParams &mp,
+                      const PartitionWorkspace &ws, const SegMap &sm, uint16_t *slots,
+                      hipStream_t stream) {
+    return launch_pass1_super<false>(p, ks, mp, ws, sm, slots, stream);
 }
 
 }  // namespace bloomhip

@@ -338,6 +338,34 @@ extern "C" int ubench_walk_choice(size_t n, int nf, const uint64_t *ms, int cu_c
     return 0;
 }
 
+// The pass-1 kernel the product chooses (choose_pass1_kernel) on a device of
+// cu_count CUs, with no device call, for n keys at `stride` bytes (4: packed,
+// 8: entry_t, both from a 16-B aligned base; else strided) and m bits:
+// slots = 0 a build (plan_build), slots = 1 a one-filter partitioned probe
+// (plan_segments).  -34: no geometry; -22: one pass 1 does not take.
+// out11: Pass1Kernel's fields in order: super, threads, layout, slots, cols,
+// mk, maxb, wgs_per_cu, nt, defer, grid.
+extern "C" int ubench_pass1_choice(size_t n, uint64_t m, int slots, size_t stride, int cu_count,
+                                   int *out11) {
+    PartitionWorkspace ws{};
+    int mode = 0;
+    if (slots) {
+        if (!plan_segments(m, cu_count, &ws)) return -34;
+        ws.tile_keys = choose_tile_keys(ws.nbins);
+        ws.ntiles = (n + ws.tile_keys - 1) / ws.tile_keys;
+    } else if (!build_plan(n, m, cu_count, &ws, &mode)) {
+        return -34;
+    }
+    const KeySpan ks{nullptr, n, stride, stride == 4 ? KEYS_PACKED : stride == 8 ? KEYS_ENTRY : KEYS_STRIDED};
+    Pass1Kernel p{};
+    SegMap sm{};
+    if (!choose_pass1_kernel(ks, make_mod_params(m), ws, slots != 0, cu_count, &p, &sm)) return -22;
+    const int out[11] = {p.super, p.threads, p.layout, p.slots, p.cols, p.mk, p.maxb, p.wgs_per_cu,
+                         p.nt, p.defer, (int)p.grid};
+    std::copy(out, out + 11, out11);
+    return 0;
+}
+
 // The product's pass 1, then pass 2 on a forced group walk (CHAINS, VECS,
 // REDIR) at G = 4, in the geometry's own mode and tile size: the four group
 // walks are right at any run length, only their speed differs
@@ -406,19 +434,20 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
     switch (variant) {
         case 0: case 20: e = launch_part_bin(ks, mp, ws, s); break;
         case 1: case 21: e = launch_part_apply(mp, words, ws, 0, s); break;
-        // pass-1 shapes with the p2 remainder (MINW, NWG)
-#define UB_P2(V, TB, MAXB, MINW, NWG)                                                             \
+        // pass-1 shapes with the p2 remainder at NWG workgroups per CU: two,
+        // and the product's (pass1_wgs_per_cu: three)
+#define UB_P2(V, TB, MAXB, NWG)                                                                   \
     case V: {                                                                                    \
         if (ws.nbins > MAXB || ws.tile_keys != TB * kPartKPT || !mp.p2) return -22;             \
         SegMap sm = seg_map_of(ws);                                                              \
         sm.p2_hi_shift = mp.p2t - sm.shift;                                                      \
-        const unsigned g = (unsigned)std::min<size_t>(ws.ntiles, (size_t)device_cu_count() * NWG); \
-        k_part_bin<KEYS_PACKED, false, true, TB, kModP2, MAXB, MINW>                             \
-            <<<g, TB, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);            \
+        k_part_bin<KEYS_PACKED, false, true, TB, kModP2, MAXB, pass1_min_waves(TB, NWG)>         \
+            <<<pass1_grid(ws.ntiles, device_cu_count(), NWG), TB, 0, s>>>(                       \
+                ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);                          \
         e = hipGetLastError();                                                                   \
         break;                                                                                   \
     }
-        UB_P2(5001, 512, 511, 4, 2) UB_P2(5003, 512, 511, 6, 3)
+        UB_P2(5001, 512, 511, 2) UB_P2(5003, 512, 511, pass1_wgs_per_cu(512, false, 511))
 #undef UB_P2
         // Pass 2 of a super-tile build (C4) over variant 0's output, by
         // k_part_apply's (G, CHAINS, VECS, REDIR): 2503 (4, 1, 2, redirected),
@@ -466,9 +495,10 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
         if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 ||           \
             ws.nbins > 511 || !runs_as_columns(ws))                                              \
             return -22;                                                                          \
-        const unsigned g = (unsigned)std::min<size_t>(ws.ntiles, (size_t)device_cu_count() * 3); \
-        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, 6, A, false, D != 0>     \
-            <<<g, 512, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);           \
+        constexpr int kWgs = pass1_wgs_per_cu(512, false, 511);                                  \
+        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), A, false, D != 0> \
+            <<<pass1_grid(ws.ntiles, device_cu_count(), kWgs), 512, 0, s>>>(                     \
+                ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);                          \
         e = hipGetLastError();                                                                   \
         break;                                                                                   \
     }
@@ -586,13 +616,14 @@ extern "C" int ubench_ladder(int variant, int tile_keys, const void *keys, size_
             if (pass1_plan(mp, ws, true, &sm) != kModLadder || ws.tile_keys != 8192) return -22;
             const bool cols = runs_as_columns(ws);
             uint32_t *rt = cols ? ws.run_starts : ws.run_rows;
-            const unsigned g = (unsigned)std::min<size_t>(ws.ntiles, (size_t)device_cu_count());
+            constexpr int kMinW = pass1_min_waves(1024, pass1_wgs_per_cu(1024, false, 1023));
+            const unsigned g = pass1_grid(ws.ntiles, device_cu_count(), pass1_wgs_per_cu(1024, false, 1023));
             if (variant == 11) {
-                if (cols) k_part_bin<KEYS_PACKED, false, true, 1024, kModLadder, 1023, 4><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
-                else k_part_bin<KEYS_PACKED, false, false, 1024, kModLadder, 1023, 4><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
+                if (cols) k_part_bin<KEYS_PACKED, false, true, 1024, kModLadder, 1023, kMinW><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
+                else k_part_bin<KEYS_PACKED, false, false, 1024, kModLadder, 1023, kMinW><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
             } else {
-                if (cols) k_part_bin<KEYS_PACKED, false, true, 1024, kModLadder, 1023, 4, 5><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
-                else k_part_bin<KEYS_PACKED, false, false, 1024, kModLadder, 1023, 4, 5><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
+                if (cols) k_part_bin<KEYS_PACKED, false, true, 1024, kModLadder, 1023, kMinW, 5><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
+                else k_part_bin<KEYS_PACKED, false, false, 1024, kModLadder, 1023, kMinW, 5><<<g, 1024, 0, s>>>(ks, mp, ws.pos, rt, sm, ws.ntiles, nullptr);
             }
             e = hipGetLastError();
             if (e == hipSuccess && !cols) e = launch_runs_transpose(ws, s);

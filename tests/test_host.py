@@ -332,6 +332,108 @@ WALK_ROWS = [
 ]
 
 
+# Pass 1's kernel per geometry (bloom_device.h choose_pass1_kernel) on a
+# 256-CU device, through the micro-benchmark library's ubench_pass1_choice (no
+# device call).  Rows: (n keys, m bits, slots: 0 = a build on plan_build, 1 =
+# a one-filter partitioned probe on plan_segments, key stride) -> Pass1Kernel's
+# fields (super, threads, layout, slots, cols, mk, maxb, workgroups per CU,
+# nt, defer, grid).  Every row was worked out by hand from the planners
+# (plan_segments, plan_build, choose_tile_keys) and from the launchers as they
+# stood before the choice became one function (launch_bin, launch_bin_tb,
+# pass1_plan, bin_launch_layout, bin_launch_fast, bin_launch,
+# part_bin_wgs_per_cu, launch_bin_super_impl, launch_bin_super_mk), not by
+# running choose_pass1_kernel.
+PACKED, ENTRY, STRIDED = 0, 1, 2
+FAST, WIDE, P2, LADDER, LADDER0, LADDER0R = 0, 1, 2, 3, 4, 5
+PASS1_ROWS = [
+    # C2 and C5's run: the kernels recorded in profiles/pass1_overlap/
+    # kernel_stats_c2_A.csv (k_part_bin<0, false, true, 512, 5, 511, 6, 0,
+    # false>: three workgroups per CU, grid 768) and kernel_stats_c5_A.csv
+    # (<0, false, true, 1024, 5, 1023, 4, 0, true>, since then also deferred).
+    # C5's run table, 8,192 tiles x 512 bins x 4 B, is exactly the 16 MiB of
+    # kColumnTableMaxBytes: columns.
+    (16_777_216, 167_772_160, 0, 4, (0, 512, PACKED, 0, 1, LADDER0R, 511, 3, 0, 0, 768)),
+    (67_108_864, 671_088_640, 0, 4, (0, 1024, PACKED, 0, 1, LADDER0R, 1023, 1, 1, 1, 256)),
+    # bin_launch's non-temporal test on C5's geometry: 4,096 tiles of 8192
+    # keys are exactly kInfinityCacheBytes (not nt), one key more is nt
+    (33_554_432, 671_088_640, 0, 4, (0, 1024, PACKED, 0, 1, LADDER0R, 1023, 1, 0, 1, 256)),
+    (33_554_433, 671_088_640, 0, 4, (0, 1024, PACKED, 0, 1, LADDER0R, 1023, 1, 1, 1, 256)),
+    # C4 (launch_bin_super_mk): 2,458 segments on 16,384 super-tiles, m =
+    # 3 << 30 on segments of 2^18 bits x 5 is kModP2; the run table (161 MB)
+    # goes out as rows and is transposed
+    (268_435_456, 3 << 30, 0, 4, (1, 1024, PACKED, 0, 0, P2, 4095, 1, 0, 0, 256)),
+    # the f = 10 tree's level-2 build: 505 segments (not a p2 form: the general
+    # remainder) on 8192-key tiles, 1024 threads, deferred, 128 MiB of tiles
+    (16_777_216, 512_000_000, 0, 4, (0, 1024, PACKED, 0, 1, FAST, 1023, 1, 0, 1, 256)),
+    # bin_launch_layout's reduction kinds: m = 2^32 is kModWide at the largest
+    # capacity (3,277 segments, 123 tiles); m = 100,000,007 the general
+    # remainder on 255 segments of 4096-key tiles (245 tiles)
+    (1_000_000, 2**32, 0, 4, (0, 1024, PACKED, 0, 1, WIDE, 8192, 1, 0, 1, 123)),
+    (1_000_000, 100_000_007, 0, 4, (0, 512, PACKED, 0, 1, FAST, 511, 3, 0, 0, 245)),
+    # m = 3 << 26: plan_segments gives 256 segments of 3 << 18 bits, a power of
+    # two of them on a p2 form, so plan_build makes it a one-member ladder
+    # (s = 18, t = 26: relabelled) and the BUILD is kModLadder0R, not kModP2;
+    # the probe of that filter (plan_segments alone) is the kModP2 row below.
+    # A build on kModP2 needs p2 segments that are no power of two:
+    # m = 51 << 23 (503 segments of 26 << 15 bits).
+    (1_000_000, 3 << 26, 0, 4, (0, 512, PACKED, 0, 1, LADDER0R, 511, 3, 0, 0, 245)),
+    (1_000_000, 51 << 23, 0, 4, (0, 1024, PACKED, 0, 1, P2, 1023, 1, 0, 1, 123)),
+    # key layouts on C2's geometry (bin_launch_layout): entry_t runs keep the
+    # small capacity; strided keys take kPartMaxBins and with it two
+    # workgroups per CU, not three
+    (16_777_216, 167_772_160, 0, 8, (0, 512, ENTRY, 0, 1, LADDER0R, 511, 3, 0, 0, 768)),
+    (16_777_216, 167_772_160, 0, 12, (0, 512, STRIDED, 0, 1, LADDER0R, 4096, 2, 0, 0, 512)),
+    # bin_launch_fast's capacity steps at 1024 threads, on probes (a build on
+    # 1,024-4,095 segments of m < 2^32 sorts super-tiles): 1,023 | 1,024
+    # segments (m = 10,230 << 17 and 5 << 28: 10 sub-blocks of 2^17 bits per
+    # segment) and 2,047 | 2,048 (m = 10,235 << 18 and 2,684,354,559: 5
+    # sub-blocks of 2^18); and 2,048 bins on a build's ladder (m = 5 << 29),
+    # deferred and above the nt capacity.  The step 511 | 512 at 512 threads
+    # cannot be reached from the planners: choose_tile_keys gives every
+    # geometry of more than 256 segments the 8192-key tile, so 512 threads
+    # sort at most 256 segments (MAXB 511, or kPartMaxBins for strided keys).
+    (1_000_000, 10_230 << 17, 1, 4, (0, 1024, PACKED, 1, 1, FAST, 1023, 1, 0, 0, 123)),
+    (1_000_000, 5 << 28, 1, 4, (0, 1024, PACKED, 1, 1, P2, 2047, 1, 0, 0, 123)),
+    (1_000_000, 10_235 << 18, 1, 4, (0, 1024, PACKED, 1, 1, FAST, 2047, 1, 0, 0, 123)),
+    (1_000_000, 2_684_354_559, 1, 4, (0, 1024, PACKED, 1, 1, FAST, 4095, 1, 0, 0, 123)),
+    (1_000_000, 5 << 29, 0, 4, (0, 1024, PACKED, 0, 1, LADDER0R, 4095, 1, 0, 1, 123)),
+    # partitioned probes (launch_bin_tb<true, TB>): 256 segments on 4096-key
+    # tiles, two workgroups per CU even at MAXB 511 (4,096 tiles: grid 512);
+    # C5's filter on 512 segments of 8192-key tiles: 1024 threads and neither
+    # deferred nor nt with the slot plane
+    (16_777_216, 3 << 26, 1, 4, (0, 512, PACKED, 1, 1, P2, 511, 2, 0, 0, 512)),
+    (16_777_216, 671_088_640, 1, 4, (0, 1024, PACKED, 1, 1, P2, 1023, 1, 0, 0, 256)),
+]
+
+
+def _pass1_choice(n, m, slots, stride):
+    bh.lib()  # torch's HIP runtime first (bloomhip._lib): one runtime per process
+    ub = ctypes.CDLL(os.path.join(os.path.dirname(bh.LIB_PATH), "libbloomhip_ubench.so"))
+    ub.ubench_pass1_choice.argtypes = [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t,
+                                       ctypes.c_int, ctypes.c_void_p]
+    out = np.zeros(11, dtype=np.int32)
+    return ub.ubench_pass1_choice(n, m, slots, stride, 256, out.ctypes.data), tuple(int(x) for x in out)
+
+
+@pytest.mark.parametrize("n,m,slots,stride,want", PASS1_ROWS)
+def test_pass1_kernel_choice(n, m, slots, stride, want):
+    assert _pass1_choice(n, m, slots, stride) == (0, want)
+
+
+def test_pass1_kernel_choice_refusal():
+    """m = 2^40 has no segment geometry (a segment of 2^26 bits exceeds the
+    LDS image): refused (-34) before a kernel is chosen.  choose_pass1_kernel's
+    own refusals (-22: more segments than the family's histogram holds, a
+    one-member ladder with slots, a ladder whose bits do not add up to t, a
+    super-tile kind other than kModP2 / kModFast) guard against geometries
+    plan_build and plan_segments do not produce: they cap the segments per
+    tile size, make ladders from p2 forms only and super-tiles for m < 2^32
+    only, so none is reachable from here."""
+    for slots in (0, 1):
+        status, out = _pass1_choice(1_000_000, 1 << 40, slots, 4)
+        assert status == -34 and out == (0,) * 11
+
+
 @pytest.mark.parametrize("n,ms,want", WALK_ROWS)
 def test_pass2_walk_choice(n, ms, want):
     bh.lib()  # torch's HIP runtime first (bloomhip._lib): one runtime per process

@@ -6,8 +6,9 @@ between two builds of libbloomhip, in child processes on one GPU: A =
 cs265-lsm-tree_amd/lib_alt (tools/build_alt.sh REV), B = lib/.  Workloads:
 c2 (16.8M keys, m = 5 << 25), f10 (16.8M keys, m = 512,000,000), c5 (67M keys,
 m = 5 << 27).  Each child prewarms 0.5 s, then times 50 builds with HIP events
-on the launch stream; rounds alternate B A B A.
-Usage: python tools/build_ab.py [rounds] [c2|f10|c5]"""
+on the launch stream; rounds alternate B A B A, or A B A B with a third
+argument A (run both orders where a figure is close).
+Usage: python tools/build_ab.py [rounds] [c2|f10|c5] [B|A]"""
 import json
 import os
 import subprocess
@@ -51,10 +52,11 @@ print(json.dumps({"build_ms": round(ms, 5), "gkeys_s": round(keys.size / ms / 1e
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
     workload = sys.argv[2] if len(sys.argv) > 2 else "c2"
+    order = ("A", "B") if len(sys.argv) > 3 and sys.argv[3] == "A" else ("B", "A")
     alt = os.path.join(ROOT, "cs265-lsm-tree_amd", "lib_alt", "libbloomhip.so")
     res = {"A": [], "B": []}
     for r in range(rounds):
-        for v in ("B", "A"):
+        for v in order:
             env = dict(os.environ)
             env.pop("BLOOMHIP_LIB", None)
             if v == "A":

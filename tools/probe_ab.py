@@ -6,8 +6,9 @@ Workload c3 (default) or f10 (the f = 10 tree's three levels; its GETs are
 routed over the three level runs the same way).
 Each child prewarms, then times 50 probe calls (HIP events on the launch
 stream) and 30 routing calls; rounds alternate B A B A so clock drift hits
-both alike.
-Usage: python tools/probe_ab.py [rounds] [c3|f10]"""
+both alike, or A B A B with a third argument A (run both orders where a
+figure is close: the side a round starts with follows an idle GPU).
+Usage: python tools/probe_ab.py [rounds] [c3|f10] [B|A]"""
 import json
 import os
 import subprocess
@@ -54,10 +55,11 @@ print(json.dumps({"probe_ms": round(p, 4), "route_ms": round(r, 4),
 def main():
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 3
     workload = sys.argv[2] if len(sys.argv) > 2 else "c3"
+    order = ("A", "B") if len(sys.argv) > 3 and sys.argv[3] == "A" else ("B", "A")
     alt = os.path.join(ROOT, "cs265-lsm-tree_amd", "lib_alt", "libbloomhip.so")
     res = {"A": [], "B": []}
     for r in range(rounds):
-        for v in ("B", "A"):
+        for v in order:
             env = dict(os.environ)
             env.pop("BLOOMHIP_LIB", None)
             if v == "A":
