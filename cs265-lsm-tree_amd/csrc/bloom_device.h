@@ -55,6 +55,8 @@ __device__ __forceinline__ int32_t load_key(const KeySpan &ks, size_t i) {
 // of x, so only the 5-instruction (x >> t) % d is left of the remainder.
 // SLOTS (partitioned probe): also write, per key and hash, the index its
 // position got in the sorted tile: slots[(tile*3 + h)*tile_keys + key].
+// PRIO: the issue priority (s_setprio) of the tile's phases, set inside the
+// phase barriers (below, lds_barrier_prio); 0 = none.
 // ---------------------------------------------------------------------------
 
 // Inclusive prefix sum across the 64 lanes of a wave in DPP steps (no LDS):
@@ -90,6 +92,30 @@ __device__ __forceinline__ uint32_t lshl_or_s(uint32_t a, uint32_t sh, uint32_t 
 __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
+// The same, and from the barrier on the wave issues at priority P (0-3): the
+// s_setprio sits in the barrier's own asm, so it is no scheduling boundary
+// of its own.  P < 0: lds_barrier().
+template <int P>
+__device__ __forceinline__ void lds_barrier_prio() {
+    static_assert(P <= 3, "s_setprio takes 0-3");
+    if constexpr (P < 0) lds_barrier();
+    else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier\n\ts_setprio %0" ::"n"(P) : "memory");
+}
+
+// k_part_bin's issue-priority policy PRIO = level | mode << 2, 0 = none
+// (every wave at priority 0 throughout).  The level (1-3) is held
+//   kPrioSort:    from the post-rank barrier (scan, run table, the next
+//                 tile's key loads, scatter, packing and stores) to the
+//                 hist-init barrier that opens the next tile's hash phase;
+//   kPrioScatter: from the second scan barrier (key loads, scatter, packing
+//                 and stores) to the hist-init barrier;
+//   kPrioHash:    the inverse of kPrioSort: from the hist-init barrier (the
+//                 hashing and its rank atomics) to the post-rank barrier;
+//   kPrioYoung:   by waves TB/128 .. TB/64 - 1 of each workgroup for the whole
+//                 kernel, set once, no flips.
+// pass1_prio chooses; only kPrioHash measured faster anywhere.
+constexpr int kPrioSort = 0, kPrioScatter = 1, kPrioHash = 2, kPrioYoung = 3;
+constexpr int pass1_prio_of(int mode, int level) { return level | mode << 2; }
 
 // LDS word at an absolute byte address.  Pass 2 has no static LDS, so its
 // dynamic image starts at LDS address 0 (launch_apply_g checks that once per
@@ -291,7 +317,7 @@ __device__ __forceinline__ void nt_store16(uint4 *p, const uint4 &v) {
 // without the sorted tile's stores.  A stage's unconsumed results go to one
 // store that only an impossible value takes.
 template <int LAYOUT, bool SLOTS, bool COLS, int TB, int MK, int MAXB = 0, int MINW = 4,
-          int ABL = 0, bool NT = false, bool DEFER = false>
+          int ABL = 0, bool NT = false, bool DEFER = false, int PRIO = 0>
 __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                                                        uint64_t *__restrict__ pos_out,
                                                        uint32_t *__restrict__ runs, SegMap sm,
@@ -303,6 +329,14 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
     static_assert(4 * kTilePos <= (1 << 17) && kTilePos < (1 << 16) &&
                       ((uint64_t)(kMaxB - 1) << kBinShift) < (1ull << 32),
                   "packed rank fields (bin nbins, never incremented, may wrap to 0)");
+    // PRIO: the priority each phase barrier leaves the wave at (-1: the plain
+    // barrier, no s_setprio: every barrier of PRIO = 0)
+    constexpr int kPrioLevel = PRIO & 3, kPrioMode = PRIO >> 2;
+    static_assert(PRIO == 0 || (kPrioLevel > 0 && kPrioMode <= kPrioYoung), "PRIO = level | mode << 2");
+    constexpr bool kFlips = PRIO != 0 && kPrioMode != kPrioYoung;
+    constexpr int kPrioAtHist = !kFlips ? -1 : kPrioMode == kPrioHash ? kPrioLevel : 0;
+    constexpr int kPrioAtRank = !kFlips || kPrioMode == kPrioScatter ? -1 : kPrioMode == kPrioSort ? kPrioLevel : 0;
+    constexpr int kPrioAtScan = kFlips && kPrioMode == kPrioScatter ? kPrioLevel : -1;
     // static LDS even for the 96 KiB of an 8192-key tile (gfx950 takes it);
     // dynamic LDS or a pointer to it made the compiler spill registers here
     __shared__ __attribute__((aligned(16))) uint32_t s_sorted[kTilePos];
@@ -377,7 +411,7 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
         auto live = [&](int j) { return FULL || kPartKPT * tid + j < tile_keys; };
 #pragma clang loop unroll(disable) vectorize(disable)
         for (int b = tid; b <= nb; b += TB) s_hist[b] = (uint32_t)b << kBinShift;
-        lds_barrier();  // also (!DEFER): the previous tile's s_sorted reads are done
+        lds_barrier_prio<kPrioAtHist>();  // also (!DEFER): the previous tile's s_sorted reads are done
 
         // 1. positions -> (segment, rank in segment) and the entry; the ranks
         //    are not consumed before the barrier, so all 24 LDS atomics of a
@@ -407,7 +441,7 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                 for (int h = 0; h < 3; h++) br[3 * j + h] = ent[3 * j + h] = 0;
             }
         }
-        lds_barrier();
+        lds_barrier_prio<kPrioAtRank>();
         // (ablation: the stage's results consumed by one impossible store)
         auto consume = [&]() {
             uint32_t x = 0;
@@ -461,7 +495,7 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                 }
             }
         }
-        lds_barrier();
+        lds_barrier_prio<kPrioAtScan>();
         if (next < ntiles) load_tile_keys<LAYOUT, TB>(ks, next, tid, knext);
         if constexpr (ABL == 3) {
             consume();
@@ -537,6 +571,11 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
     const size_t nfull = ks.n / kTileKeys;
     size_t tile = part_tile(0, ntiles);
     if (tile >= ntiles) return;
+    if constexpr (PRIO != 0 && kPrioMode == kPrioYoung) {
+        // the workgroup's later-dispatched half; the wave index from an SGPR,
+        // so the branch is scalar (s_setprio ignores EXEC)
+        if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(kPrioLevel);
+    }
     load_tile_keys<LAYOUT, TB>(ks, tile, tid, kcur);
     if constexpr (!DEFER) {
         for (size_t round = 0; tile < nfull; round++) {
@@ -2120,6 +2159,7 @@ struct Pass1Kernel {
     bool nt;         // NT: the sorted tiles stored non-temporal
     bool defer;      // DEFER: a tile's write-out inside the next tile's hash phase
     unsigned grid;   // persistent workgroups
+    int prio;        // PRIO: the phases' issue priority (pass1_prio_of), 0 = none
 };
 // pass 1: the unit of each family launches the kernel p names; false when it
 // holds no such kernel.  Build / probe (slots) at 512 or 1024 threads
@@ -2186,6 +2226,22 @@ inline unsigned pass1_grid(size_t ntiles, int ncu, int wgs) {
 // 0.385 ms).  With the slot plane (C3's probe) it is level, and on 512
 // threads at three workgroups per CU (C2) slower, 54.7 -> 56.0 us.
 constexpr bool pass1_defer(int threads, bool slots) { return threads >= 1024 && !slots; }
+
+// The phases' issue priority (k_part_bin's PRIO, pass1_prio_of(mode, level)).
+// It matters only where workgroups in different phases share a CU.  The
+// 512-thread builds on three workgroups per CU (C2) hash at priority 1 and
+// sort at 0: pass 1 55.1 -> 49.8 us, the C2 build 0.0887 -> 0.0841 ms
+// (0.0888 -> 0.0836 with the parent first), the median below the parent's
+// fastest run in both orders; levels 2 and 3 measure as 1.  Raising the sort
+// phases, or only scatter + packing, costs 0.5 us at any level; one static
+// level for waves 4-7 gained 0.8 us in one run and nothing in the next; the
+// static form on one 1024-thread workgroup per CU is level (C5 216.3 / 216.4
+// us, the f = 10 build 71.0 / 71.3).  Not measured, so 0: 512 threads on two
+// workgroups per CU (strided keys, m >= 2^32, the probe with its slot plane).
+// (profiles/pass1_priority/README.md; tools/ubench.py p1ab, p1abl.)
+constexpr int pass1_prio(int threads, bool slots, int wgs_per_cu) {
+    return threads == 512 && !slots && wgs_per_cu == 3 ? pass1_prio_of(kPrioHash, 1) : 0;
+}
 
 // builds whose sorted tiles exceed the Infinity Cache (C5): stored
 // non-temporal (k_part_bin's NT); compiled for the 1024-thread builds at
@@ -2258,6 +2314,7 @@ inline bool choose_pass1_kernel(const KeySpan &ks, const ModParams &mp, const Pa
     p.defer = !p.super && pass1_defer(p.threads, slots);
     p.nt = !p.super && pass1_may_nt(p.threads, slots, p.maxb) &&
            ws.ntiles * (uint64_t)(p.threads * kPartKPT) * 8 > kInfinityCacheBytes;
+    p.prio = p.super ? 0 : pass1_prio(p.threads, slots, p.wgs_per_cu);
     p.cols = runs_as_columns(ws);
     p.grid = pass1_grid(ws.ntiles, ncu, p.wgs_per_cu);
     *out = p;
@@ -2292,10 +2349,11 @@ bool launch_pass1_tile(const Pass1Kernel &p, const KeySpan &ks, const ModParams 
                     constexpr int kWgs = pass1_wgs_per_cu(TB, SLOTS, MAXB);
                     constexpr int kMinW = pass1_min_waves(TB, kWgs);
                     constexpr bool kMayNT = pass1_may_nt(TB, SLOTS, MAXB);
-                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT)) return false;
+                    constexpr int kPrio = pass1_prio(TB, SLOTS, kWgs);
+                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT) || p.prio != kPrio) return false;
                     auto go = [&](auto cols_c, auto nt_c) {
                         k_part_bin<L, SLOTS, decltype(cols_c)::value, TB, MK, MAXB, kMinW, 0,
-                                   decltype(nt_c)::value, kDefer>
+                                   decltype(nt_c)::value, kDefer, kPrio>
                             <<<p.grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
                     };
                     if constexpr (kMayNT) {

@@ -143,12 +143,26 @@ __global__ void ub_rawhash(int iters, uint32_t *sink) {
 // VALU / LDS overlap probe: waves of the first `valu_waves` of each 16-wave
 // workgroup run the hash+mod loop, the others random LDS ds_add_rtn (mode 0:
 // both, 1: hash waves only (others exit), 2: LDS waves only).
+// prio: the issue priority (s_setprio 0-3) of the LDS waves in bits 0-1 and of
+// the hash waves in bits 2-3, set once after the barrier.  The wave's kind
+// comes from an SGPR there, so the choice is a scalar branch: s_setprio
+// ignores EXEC, and under a divergent `if` every wave would run it.
+__device__ __forceinline__ void ub_set_prio(int p) {
+    if (p == 1) __builtin_amdgcn_s_setprio(1);
+    else if (p == 2) __builtin_amdgcn_s_setprio(2);
+    else if (p == 3) __builtin_amdgcn_s_setprio(3);
+}
 template <int OP>  // LDS op of the non-hashing waves: 0 ds_add_rtn, 1 ds_write, 2 ds_read
 __global__ void __launch_bounds__(1024) ub_mixed(ModParams mp, int valu_waves, int mode,
-                                                 int hash_iters, int lds_iters, uint32_t *sink) {
+                                                 int hash_iters, int lds_iters, uint32_t *sink,
+                                                 int prio) {
     extern __shared__ uint32_t seg[];
     for (int i = threadIdx.x; i < 16384; i += blockDim.x) seg[i] = 0;
     __syncthreads();
+    if (prio) {
+        const bool hashes = (__builtin_amdgcn_readfirstlane(threadIdx.x) >> 6) < valu_waves;
+        ub_set_prio(hashes ? (prio >> 2) & 3 : prio & 3);
+    }
     const int wave = threadIdx.x >> 6;
     if (wave < valu_waves) {
         if (mode == 2) return;
@@ -211,17 +225,19 @@ extern "C" int ubench_run(int which, void *dbuf, size_t bytes, uint64_t m, int g
         case 42: ub_lds_or_idle<2><<<grid, 1024, 66 * 1024, s>>>(iters, sink); break;
         case 43: ub_lds_or_idle<3><<<grid, 1024, 66 * 1024, s>>>(iters, sink); break;
         case 44: ub_lds_or_idle<4><<<grid, 1024, 66 * 1024, s>>>(iters, sink); break;
-        case 10: case 11: case 12:  // block = waves doing VALU (of 16), iters = hash iters
+        // block = waves doing VALU (of 16), iters = hash iters; m (no filter
+        // here) = the priorities: LDS waves' in bits 0-1, hash waves' in 2-3
+        case 10: case 11: case 12:
             ub_mixed<0><<<grid, 1024, 65536, s>>>(make_mod_params(167772160), block, which - 10,
-                                                  iters, iters * 6, sink);
+                                                  iters, iters * 6, sink, (int)(m & 15));
             break;
         case 20: case 21: case 22:
             ub_mixed<1><<<grid, 1024, 65536, s>>>(make_mod_params(167772160), block, which - 20,
-                                                  iters, iters * 6, sink);
+                                                  iters, iters * 6, sink, (int)(m & 15));
             break;
         case 30: case 31: case 32:
             ub_mixed<2><<<grid, 1024, 65536, s>>>(make_mod_params(167772160), block, which - 30,
-                                                  iters, iters * 6, sink);
+                                                  iters, iters * 6, sink, (int)(m & 15));
             break;
         default: return -22;
     }
@@ -343,10 +359,8 @@ extern "C" int ubench_walk_choice(size_t n, int nf, const uint64_t *ms, int cu_c
 // 8: entry_t, both from a 16-B aligned base; else strided) and m bits:
 // slots = 0 a build (plan_build), slots = 1 a one-filter partitioned probe
 // (plan_segments).  -34: no geometry; -22: one pass 1 does not take.
-// out11: Pass1Kernel's fields in order: super, threads, layout, slots, cols,
-// mk, maxb, wgs_per_cu, nt, defer, grid.
-extern "C" int ubench_pass1_choice(size_t n, uint64_t m, int slots, size_t stride, int cu_count,
-                                   int *out11) {
+namespace {
+int pass1_choice_of(size_t n, uint64_t m, int slots, size_t stride, int cu_count, Pass1Kernel *out) {
     PartitionWorkspace ws{};
     int mode = 0;
     if (slots) {
@@ -357,12 +371,33 @@ extern "C" int ubench_pass1_choice(size_t n, uint64_t m, int slots, size_t strid
         return -34;
     }
     const KeySpan ks{nullptr, n, stride, stride == 4 ? KEYS_PACKED : stride == 8 ? KEYS_ENTRY : KEYS_STRIDED};
-    Pass1Kernel p{};
     SegMap sm{};
-    if (!choose_pass1_kernel(ks, make_mod_params(m), ws, slots != 0, cu_count, &p, &sm)) return -22;
+    if (!choose_pass1_kernel(ks, make_mod_params(m), ws, slots != 0, cu_count, out, &sm)) return -22;
+    return 0;
+}
+}  // namespace
+
+// out11: Pass1Kernel's fields in order: super, threads, layout, slots, cols,
+// mk, maxb, wgs_per_cu, nt, defer, grid.
+extern "C" int ubench_pass1_choice(size_t n, uint64_t m, int slots, size_t stride, int cu_count,
+                                   int *out11) {
+    Pass1Kernel p{};
+    const int rc = pass1_choice_of(n, m, slots, stride, cu_count, &p);
+    if (rc) return rc;
     const int out[11] = {p.super, p.threads, p.layout, p.slots, p.cols, p.mk, p.maxb, p.wgs_per_cu,
                          p.nt, p.defer, (int)p.grid};
     std::copy(out, out + 11, out11);
+    return 0;
+}
+
+// The issue priority of that kernel's phases (Pass1Kernel::prio,
+// pass1_prio_of(mode, level); 0 = none), same arguments and status.
+extern "C" int ubench_pass1_prio(size_t n, uint64_t m, int slots, size_t stride, int cu_count,
+                                 int *prio_out) {
+    Pass1Kernel p{};
+    const int rc = pass1_choice_of(n, m, slots, stride, cu_count, &p);
+    if (rc) return rc;
+    *prio_out = p.prio;
     return 0;
 }
 
@@ -506,6 +541,55 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
         // (stages 1-4 write no tile out: the same with and without DEFER)
         UB_ABL(0, 1) UB_ABL(5, 1)
 #undef UB_ABL
+        // 5200 + 10 * PRIO + ABL: 5100 + ABL with the phases at an issue
+        // priority (k_part_bin's PRIO = level | mode << 2): the sort phases
+        // at level 1, 2, 3 (PRIO 1, 2, 3), only scatter + packing at 1
+        // (PRIO 5), the inverse, the hash phase at 1, 2, 3 (PRIO 9, 10, 11),
+        // and waves 4-7 of each workgroup at a static 1 (PRIO 13).  The
+        // ladders start at stage 3: stages 1 and 2 end at the post-rank
+        // barrier, where a tile's first flip is.
+#define UB_PRIO(P, A)                                                                             \
+    case 5200 + 10 * P + A: {                                                                    \
+        SegMap sm{};                                                                             \
+        if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 ||           \
+            ws.nbins > 511 || !runs_as_columns(ws))                                              \
+            return -22;                                                                          \
+        constexpr int kWgs = pass1_wgs_per_cu(512, false, 511);                                  \
+        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), A, false, false, P> \
+            <<<pass1_grid(ws.ntiles, device_cu_count(), kWgs), 512, 0, s>>>(                     \
+                ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);                          \
+        e = hipGetLastError();                                                                   \
+        break;                                                                                   \
+    }
+#define UB_PRIO_LADDER(P) UB_PRIO(P, 0) UB_PRIO(P, 3) UB_PRIO(P, 4) UB_PRIO(P, 5)
+        UB_PRIO_LADDER(pass1_prio_of(kPrioSort, 1)) UB_PRIO_LADDER(pass1_prio_of(kPrioSort, 2))
+        UB_PRIO_LADDER(pass1_prio_of(kPrioSort, 3)) UB_PRIO_LADDER(pass1_prio_of(kPrioScatter, 1))
+        UB_PRIO_LADDER(pass1_prio_of(kPrioHash, 1)) UB_PRIO(pass1_prio_of(kPrioHash, 2), 0)
+        UB_PRIO(pass1_prio_of(kPrioHash, 3), 0) UB_PRIO(pass1_prio_of(kPrioYoung, 1), 0)
+#undef UB_PRIO_LADDER
+#undef UB_PRIO
+        // 5413: the 1024-thread builds' pass 1 (one workgroup per CU, write-out
+        // deferred) with waves 8-15 at a static priority 1: C5 (one-member
+        // ladder, 512 bins, non-temporal tiles) and the f = 10 tree's level-2
+        // build (the general remainder, 505 segments)
+        case 5413: {
+            SegMap sm{};
+            const int mk = pass1_plan(mp, ws, false, &sm);
+            constexpr int kP = pass1_prio_of(kPrioYoung, 1);
+            if (ws.tile_keys != 8192 || ws.nbins > 1023 || !runs_as_columns(ws)) return -22;
+            const unsigned grid = pass1_grid(ws.ntiles, device_cu_count(), 1);
+            const bool nt = ws.ntiles * (uint64_t)8192 * 8 > kInfinityCacheBytes;
+            if (mk == kModLadder0R && nt)
+                k_part_bin<KEYS_PACKED, false, true, 1024, kModLadder0R, 1023, 4, 0, true, true, kP>
+                    <<<grid, 1024, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);
+            else if (mk == kModFast && !nt)
+                k_part_bin<KEYS_PACKED, false, true, 1024, kModFast, 1023, 4, 0, false, true, kP>
+                    <<<grid, 1024, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);
+            else
+                return -22;
+            e = hipGetLastError();
+            break;
+        }
         default: return -22;
     }
     return e == hipSuccess ? 0 : -5;

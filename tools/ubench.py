@@ -116,11 +116,15 @@ def part_phases(n=16_777_216, bpe=10.0, reps=50):
                               "us": round(ms * 1e3, 1)}), flush=True)
 
 
-def p1_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
+def p1_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50, m=None):
     """Interleaved A/B of pass-1 variants (ubench_part 5xxx) against the
     product (0): each variant's output goes through the product's pass 2
-    and must give the product's bitmap; then rounds x variants timed."""
-    run, words, geo = _part_setup(n, bpe)
+    and must give the product's bitmap; then rounds x variants timed.
+    The priority variants of C2's pass 1 are 5200 + 10 * PRIO (k_part_bin's
+    PRIO: 1-3 the sort phases at that level, 5 scatter + packing at 1, 9 the
+    hash phase at 1, 13 waves 4-7 at a static 1); 5413 is the static form on
+    the 1024-thread builds (p1ab_c5, p1ab_f10)."""
+    run, words, geo = _part_setup(n, bpe, m)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
     ref = words.clone()
@@ -181,7 +185,7 @@ def p2_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
               flush=True)
 
 
-def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50):
+def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50, prios=()):
     """C2's pass 1 cut after each stage (ubench_part 5100 + 20 * DEFER + ABL,
     k_part_bin's ABL): 1 hash + bin/entry, 2 + rank atomics, 3 + scan and run
     table, 4 + scatter (the image read once), 5 + packing (no tile stores),
@@ -190,12 +194,13 @@ def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50):
     tile's own scatter (DEFER 0: 5105, 5100) and deferred into the next
     tile's hash phase (5125, 5120).  5100 and 5120 must
     give the product's bitmap through the product's pass 2; interleaved
-    rounds."""
+    rounds.  prios (`p1abl 1,2,5`): k_part_bin's PRIO values whose stages
+    3, 4, 5 and 0 (5200 + 10 * PRIO + ABL) are priced in the same rounds."""
     run, words, geo = _part_setup(n, bpe)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
     ref = words.clone()
-    for v in (5100, 5120):
+    for v in (5100, 5120) + tuple(5200 + 10 * p for p in prios):
         words.zero_()
         assert run(v) == 0 and run(1) == 0
         torch.cuda.synchronize()
@@ -206,6 +211,8 @@ def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50):
              5100: "whole pass 1, write-out after the scatter",
              5125: "+ packing deferred (no stores)", 5120: "whole pass 1, write-out deferred",
              0: "product pass 1"}
+    for p in prios:
+        names.update({5200 + 10 * p + a: f"PRIO {p}: {names[5100 + a]}" for a in (3, 4, 5, 0)})
     _prewarm(run, 0)
     res = {v: [] for v in names}
     for _ in range(rounds):
@@ -390,19 +397,23 @@ def ladder_ablation(levels_sel=(0, 1, 2, 3, 4), reps=20):
                                   "us": round(t * 1e3, 1)}), flush=True)
 
 
-def mixed():
+def mixed(prios=((0, 0),)):
     """Can LDS atomics and VALU hashing overlap on a CU?  Some of 16 waves
-    hash, the rest do random ds_add_rtn: time both together vs each alone."""
+    hash, the rest do random ds_add_rtn: time both together vs each alone.
+    prios: (LDS waves' s_setprio, hash waves' s_setprio) pairs; `mixed prio`
+    runs the LDS waves at 0-3 beside hash waves at 0, then the inverse."""
     buf = torch.zeros(1 << 20, dtype=torch.int32, device="cuda")
     nb = buf.numel() * 4
     for base, lds_op in ((10, "ds_add_rtn"), (20, "ds_write"), (30, "ds_read")):
       for vw in (8, 4, 12):
-        t = {}
-        for mode, name in ((0, "both"), (1, "valu only"), (2, "lds only")):
-            t[name] = timeit(base + mode, buf, nb, 0, 512, vw, 64)
-        print(json.dumps({"op": "valu/lds overlap", "lds_op": lds_op, "valu_waves": vw,
-                          **{k: round(v * 1e3, 1) for k, v in t.items()},
-                          "sum": round((t["valu only"] + t["lds only"]) * 1e3, 1)}), flush=True)
+        for lds_prio, valu_prio in prios:
+            t = {}
+            for mode, name in ((0, "both"), (1, "valu only"), (2, "lds only")):
+                t[name] = timeit(base + mode, buf, nb, lds_prio | valu_prio << 2, 512, vw, 64)
+            print(json.dumps({"op": "valu/lds overlap", "lds_op": lds_op, "valu_waves": vw,
+                              "lds_prio": lds_prio, "valu_prio": valu_prio,
+                              **{k: round(v * 1e3, 1) for k, v in t.items()},
+                              "sum": round((t["valu only"] + t["lds only"]) * 1e3, 1)}), flush=True)
 
 
 LIB.ubench_cal.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int,
@@ -542,6 +553,8 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "transpose":
         return transpose()
     if len(sys.argv) > 1 and sys.argv[1] == "mixed":
+        if len(sys.argv) > 2 and sys.argv[2] == "prio":
+            return mixed(((0, 0), (1, 0), (2, 0), (3, 0), (0, 1), (0, 3)))
         return mixed()
     if len(sys.argv) > 1 and sys.argv[1] == "cal":
         return cal()
@@ -571,7 +584,11 @@ def main():
                                   "ms": round(ms, 4)}), flush=True)
         return
     if len(sys.argv) > 1 and sys.argv[1] == "p1abl":
-        return p1_ablation()
+        return p1_ablation(prios=tuple(int(p) for p in sys.argv[2].split(",")) if len(sys.argv) > 2 else ())
+    if len(sys.argv) > 1 and sys.argv[1] == "p1ab_c5":
+        return p1_ab([5413], 67_108_864, 10.0, 3, 20)
+    if len(sys.argv) > 1 and sys.argv[1] == "p1ab_f10":
+        return p1_ab([5413], m=512_000_000)
     if len(sys.argv) > 1 and sys.argv[1] == "p1tail":
         return p1_tail()
     if len(sys.argv) > 1 and sys.argv[1] == "part":
