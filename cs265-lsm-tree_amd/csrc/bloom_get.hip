@@ -17,7 +17,7 @@
 // 4096, src/run.cpp:101-103, while Run::put places a fence every 4096
 // ENTRIES, :164: 512 entries at the wrong place for every page > 0.  The
 // interval the fences describe is searched here)
-#include "bloom_device.h"
+#include "bloom_combine.h"  // route_page
 
 #include <algorithm>
 

@@ -27,9 +27,12 @@
 //
 // This unit: the atomic and LDS builds, the gather and LDS probes, run
 // metadata and GET routing, the scalar calls, and the geometry planners.
-// The partition kernels are in bloom_device.h (one translation unit per
-// instantiation family: bloom_pass1_*.hip, bloom_pass2.hip, bloom_probe*.hip).
-#include "bloom_device.h"
+// The partition kernels are in bloom_pass1.h, bloom_pass2.h and
+// bloom_combine.h (one translation unit per instantiation family:
+// bloom_pass1_*.hip, bloom_pass2.hip, bloom_probe*.hip); this unit launches
+// pass 1 of the builds through launch_bin and searches pages with route_page.
+#include "bloom_combine.h"
+#include "bloom_pass1.h"
 
 #include <stdlib.h>
 

@@ -1,7 +1,7 @@
 // bloom_pass1_build1024.hip — pass 1 of the partition build (no slots) at
 // 1024 threads per workgroup (8192-key tiles): every key layout and
-// remainder kind of k_part_bin (bloom_device.h), in one translation unit.
-#include "bloom_device.h"
+// remainder kind of k_part_bin (bloom_pass1.h), in one translation unit.
+#include "bloom_pass1.h"
 
 namespace bloomhip {
 

@@ -1,6 +1,6 @@
 // bloom_pass1_super.hip — pass 1 of the partition build on super-tiles of
-// 16,384 keys (k_part_bin2, bloom_device.h): builds with many short runs.
-#include "bloom_device.h"
+// 16,384 keys (k_part_bin2, bloom_pass1.h): builds with many short runs.
+#include "bloom_pass1.h"
 
 namespace bloomhip {
 

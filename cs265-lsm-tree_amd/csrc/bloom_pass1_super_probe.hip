@@ -1,7 +1,7 @@
 // bloom_pass1_super_probe.hip — pass 1 of the stacked probe on super-tiles
-// of 16,384 keys (k_part_bin2 with the slot plane, bloom_device.h): segment
+// of 16,384 keys (k_part_bin2 with the slot plane, bloom_pass1.h): segment
 // stacks with many short runs (the f = 10 tree's 1,250 segments).
-#include "bloom_device.h"
+#include "bloom_pass1.h"
 
 namespace bloomhip {
 

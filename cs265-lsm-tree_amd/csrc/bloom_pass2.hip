@@ -1,6 +1,6 @@
 // bloom_pass2.hip — pass 2 of the partition build (k_part_apply in build
-// modes, bloom_device.h): segments or plan_build's one-member ladder.
-#include "bloom_device.h"
+// modes, bloom_pass2.h): segments or plan_build's one-member ladder.
+#include "bloom_pass2.h"
 
 namespace bloomhip {
 

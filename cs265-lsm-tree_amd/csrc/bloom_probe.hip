@@ -1,6 +1,9 @@
 // bloom_probe.hip — the partitioned and stacked probes: pass 2 in probe and
-// segment-stack modes, the combine, and the launch sequences (bloom_device.h).
-#include "bloom_device.h"
+// segment-stack modes, the combine, and the launch sequences (bloom_pass1.h,
+// bloom_pass2.h, bloom_combine.h).
+#include "bloom_combine.h"
+#include "bloom_pass1.h"
+#include "bloom_pass2.h"
 
 namespace bloomhip {
 

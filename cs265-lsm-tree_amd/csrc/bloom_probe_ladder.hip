@@ -1,6 +1,6 @@
 // bloom_probe_ladder.hip — pass 2 of the ladder stack (k_part_apply in
-// kApplyLadder mode for every member count and direct count, bloom_device.h).
-#include "bloom_device.h"
+// kApplyLadder mode for every member count and direct count, bloom_pass2.h).
+#include "bloom_pass2.h"
 
 namespace bloomhip {
 

@@ -10,7 +10,10 @@
 #include <algorithm>
 #include <numeric>
 
-#include "bloom_device.h"  // the product kernels and launch templates, for ablation builds
+// the product kernels and launch templates, for ablation builds
+#include "bloom_combine.h"
+#include "bloom_pass1.h"
+#include "bloom_pass2.h"
 #include "bloom_merge.h"
 
 using namespace bloomhip;

@@ -294,7 +294,7 @@ def test_planner_magic_bound_implies_exact(shift):
         assert np.array_equal(got, want), g
 
 
-# Pass 2's walk per geometry (bloom_device.h choose_apply_walk) on a 256-CU
+# Pass 2's walk per geometry (bloom_pass2.h choose_apply_walk) on a 256-CU
 # device, through the micro-benchmark library's ubench_walk_choice (no device
 # call).  Rows: (n keys, filter sizes: one = a build, several = a stacked
 # probe) -> (mode, tile keys, segments, G, CHAINS, VECS, REDIR).  C2 and C5
@@ -332,7 +332,7 @@ WALK_ROWS = [
 ]
 
 
-# Pass 1's kernel per geometry (bloom_device.h choose_pass1_kernel) on a
+# Pass 1's kernel per geometry (bloom_pass1.h choose_pass1_kernel) on a
 # 256-CU device, through the micro-benchmark library's ubench_pass1_choice (no
 # device call).  Rows: (n keys, m bits, slots: 0 = a build on plan_build, 1 =
 # a one-filter partitioned probe on plan_segments, key stride) -> Pass1Kernel's

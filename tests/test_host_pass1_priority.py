@@ -1,4 +1,4 @@
-"""The issue priority of pass 1's phases per geometry (bloom_device.h
+"""The issue priority of pass 1's phases per geometry (bloom_pass1.h
 pass1_prio, Pass1Kernel::prio) on a 256-CU device, through the micro-benchmark
 library's ubench_pass1_prio: no device call, no GPU.
 

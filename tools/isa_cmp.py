@@ -4,11 +4,8 @@
 (comments and directives dropped, the kernel's own symbol replaced, block
 labels renumbered) and the -Rpass-analysis=kernel-resource-usage lines.
 Prints one line per kernel (same / DIFF, instruction lines, a digest of the
-stream, registers, spills, LDS, occupancy) and the counts per unit.
-A k_part_bin that names its issue-priority policy (an eleventh template
-argument PRIO, absent at the parent) is compared with the parent's kernel of
-the same other arguments: identical for PRIO 0; with a priority, identical
-but for its s_setprio lines, and listed apart.
+stream, registers, spills, LDS, occupancy) and the counts per unit.  Kernels
+are paired by their mangled names.
 Usage: python tools/isa_cmp.py PARENT_OBJ NEW_OBJ UNIT..."""
 import hashlib
 import re
@@ -76,40 +73,6 @@ def resources(path):
     return res
 
 
-def part_bin_prio(demangled):
-    """(name without PRIO, PRIO) of a k_part_bin that carries its eleventh
-    template argument PRIO, else None."""
-    m = re.search(r"k_part_bin<([^<>]*)>", demangled)
-    if not m:
-        return None
-    args = [a.strip() for a in m.group(1).split(",")]
-    if len(args) != 11:
-        return None
-    return demangled.replace(m.group(0), "k_part_bin<%s>" % ", ".join(args[:10])), int(args[10])
-
-
-def rename_to_parent(kb, rb, ka):
-    """k_part_bin gained a last template argument PRIO, which is in every
-    mangled name: a kernel with PRIO 0 is compared under the parent's name for
-    the same other arguments; one with a priority is returned apart, with the
-    parent's kernel it must differ from by its s_setprio lines alone."""
-    da = demangle(sorted(ka))
-    by_dem = {v: k for k, v in da.items()}
-    db = demangle(sorted(kb))
-    out_k, out_r, raised = {}, {}, []
-    for k, body in kb.items():
-        pp = part_bin_prio(db[k])
-        if pp and pp[0] in by_dem and k not in ka:
-            parent = by_dem[pp[0]]
-            if pp[1] == 0:
-                out_k[parent], out_r[parent] = body, rb.get(k)
-            else:
-                raised.append((db[k], pp[1], parent, body, rb.get(k)))
-            continue
-        out_k[k], out_r[k] = body, rb.get(k)
-    return out_k, out_r, raised
-
-
 def main():
     pa, nb = sys.argv[1], sys.argv[2]
     tot = [0, 0, 0]
@@ -118,29 +81,10 @@ def main():
         kb = kernels(f"{nb}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
         ra = resources(f"{pa}/resource_usage_{unit}.txt")
         rb = resources(f"{nb}/resource_usage_{unit}.txt")
-        kb, rb, raised = rename_to_parent(kb, rb, ka)
-        n_parent, n_now = len(ka), len(kb) + len(raised)
         differing = 0
-        prio_lines = []
-        ka0 = dict(ka)
-        for name, prio, parent, body, res in raised:
-            rest = [l for l in body if not l.startswith("s_setprio")]
-            ok = rest == ka0[parent] and res == ra.get(parent)
-            r = dict(x.split(":", 1) for x in ra.get(parent, []) if ":" in x)
-            name = re.sub(r"^void bloomhip::\(anonymous namespace\)::", "", name).split("(bloomhip::")[0]
-            prio_lines.append(
-                f"  PRIO {prio} {'only s_setprio added' if ok else 'DIFFERS beyond s_setprio'} "
-                f"{name}: {len(ka0[parent])} -> {len(body)} lines (+{len(body) - len(rest)} s_setprio), "
-                f"resources {'same' if res == ra.get(parent) else 'DIFF'}; VGPRs{r.get('VGPRs', '?')} "
-                f"spill{r.get('VGPRs Spill', '?')} LDS{r.get('LDS Size [bytes/block]', '?')} "
-                f"occ{r.get('Occupancy [waves/SIMD]', '?')}")
-            differing += not ok
-            if parent not in kb:
-                ka.pop(parent, None)  # compared above, with its PRIO 0 form gone from the unit
         dm = demangle(sorted(set(ka) | set(kb)))
-        print(f"== {unit}: kernels at the parent {n_parent}, now {n_now}; with a priority {len(raised)}; "
+        print(f"== {unit}: kernels at the parent {len(ka)}, now {len(kb)}; "
               f"only at the parent {len(set(ka) - set(kb))}, only now {len(set(kb) - set(ka))}")
-        print("\n".join(sorted(prio_lines)) if prio_lines else "  (no kernel with a priority)")
         for k in sorted(set(ka) - set(kb)):
             print("  ONLY PARENT", dm[k])
         for k in sorted(set(kb) - set(ka)):
@@ -158,8 +102,8 @@ def main():
                   f"SGPRs{r.get('TotalSGPRs', '?')} spill{r.get('VGPRs Spill', '?')} "
                   f"LDS{r.get('LDS Size [bytes/block]', '?')} occ{r.get('Occupancy [waves/SIMD]', '?')}")
         print(f"== {unit}: differing {differing}")
-        tot[0] += n_parent
-        tot[1] += n_now
+        tot[0] += len(ka)
+        tot[1] += len(kb)
         tot[2] += differing
     print(f"== total: parent {tot[0]}, now {tot[1]}, differing {tot[2]}")
 
