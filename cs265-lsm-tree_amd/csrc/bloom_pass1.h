@@ -36,6 +36,9 @@ namespace {
 // position got in the sorted tile: slots[(tile*3 + h)*tile_keys + key].
 // PRIO: the issue priority (s_setprio) of the tile's phases, set inside the
 // phase barriers (below, lds_barrier_prio); 0 = none.
+// PIPE: the software-pipelined tile loop: a tile is scattered inside the hash
+// phase of the workgroup's next tile, key by key, on two histograms (at the
+// loop, below).
 // ---------------------------------------------------------------------------
 
 // k_part_bin's issue-priority policy PRIO = level | mode << 2, 0 = none
@@ -198,9 +201,12 @@ __device__ __forceinline__ void bin_entry(uint64_t raw, const ModParams &mp, con
 // atomics; 3 + the scan and the run table; 4 + the scatter (each thread reads
 // one word of the image, or the compiler drops the stage); 5 + the packing,
 // without the sorted tile's stores.  A stage's unconsumed results go to one
-// store that only an impossible value takes.
+// store that only an impossible value takes.  The same numbers cut the PIPE
+// loop: there stage 3 is the scan without any scatter and stage 4 adds the
+// scatter interleaved with the hashing (it needs the scan's offsets to stay
+// inside the image, so it cannot be priced before the scan).
 template <int LAYOUT, bool SLOTS, bool COLS, int TB, int MK, int MAXB = 0, int MINW = 4,
-          int ABL = 0, bool NT = false, bool DEFER = false, int PRIO = 0>
+          int ABL = 0, bool NT = false, bool DEFER = false, int PRIO = 0, int PIPE = 0>
 __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                                                        uint64_t *__restrict__ pos_out,
                                                        uint32_t *__restrict__ runs, SegMap sm,
@@ -223,7 +229,8 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
     // static LDS even for the 96 KiB of an 8192-key tile (gfx950 takes it);
     // dynamic LDS or a pointer to it made the compiler spill registers here
     __shared__ __attribute__((aligned(16))) uint32_t s_sorted[kTilePos];
-    __shared__ uint32_t s_hist[kMaxB + 1];
+    // (PIPE: two histograms, H[1] at word offset kMaxB + 1)
+    __shared__ uint32_t s_hist[(PIPE ? 2 : 1) * (kMaxB + 1)];
     __shared__ uint32_t s_wsum[TB / 64];
 
     const int tid = threadIdx.x;
@@ -268,6 +275,54 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
         }
     };
     constexpr bool kPacks = ABL == 0 || ABL == 5;  // the stages that write tiles out
+
+    // Exclusive scan of a histogram's nbins+1 counts (the extra slot is 0 and
+    // receives the tile total), in two halves around a workgroup barrier of
+    // the caller's; thread t owns [t*per, t*per + per).  Waves that own no
+    // bin (C2: waves 5-7 of 8) skip it: nobody reads their wave sums, which
+    // come after every live bin.  hoff: the histogram's word offset in s_hist
+    // (0 but in the PIPE loop), part of its bins' bias.
+    // first half: the thread's counts (4 * count of bin b) and the wave sums
+    auto scan_counts = [&](uint32_t hoff, uint32_t (&local)[kScanPer], uint32_t &tsum, uint32_t &incl) {
+        const bool scan_wave = wave * 64 * per <= nb;  // uniform per wave
+        tsum = incl = 0;
+        if (scan_wave) {
+#pragma unroll
+            for (int q = 0; q < kScanPer; q++) {
+                const int b = tid * per + q;
+                local[q] = (q < per && b <= nb) ? s_hist[hoff + b] - ((hoff + b) << kBinShift) : 0u;
+                tsum += local[q];
+            }
+            incl = wave_incl_scan(tsum);
+            if (lane == 63) s_wsum[wave] = incl;
+        }
+    };
+    // second half: the bins' offsets into the histogram, the run table's column
+    auto scan_offsets = [&](uint32_t hoff, size_t tile, const uint32_t (&local)[kScanPer], uint32_t tsum,
+                            uint32_t incl) {
+        if (wave * 64 * per <= nb) {
+            uint32_t run = incl - tsum;
+            for (int w = 0; w < wave; w++) run += s_wsum[w];
+#pragma unroll
+            for (int q = 0; q < kScanPer; q++) {
+                const int b = tid * per + q;
+                if (q < per && b <= nb) {
+                    // biased by -(b << kBinShift): bin + rank value = byte slot
+                    s_hist[hoff + b] = run - ((hoff + b) << kBinShift);
+                    // segment b's run of this tile, [start, end) in entries,
+                    // packed start | end << 16 (both < 3 * 8192), straight
+                    // from the scan's registers: segment-major column or
+                    // tile-major row
+                    const uint32_t pk = (run >> 2) | (((run + local[q]) >> 2) << 16);
+                    if (b < nb) {
+                        if constexpr (COLS) runs[(size_t)b * ntiles + tile] = pk;
+                        else runs[tile * (size_t)nb + b] = pk;
+                    }
+                    run += local[q];
+                }
+            }
+        }
+    };
 
     // One tile.  FULL (every tile but a short last one) makes the key count a
     // constant: no per-key guards, and a fixed number of vector-memory ops
@@ -338,46 +393,12 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
             return;
         }
 
-        // 2. exclusive scan of the nbins+1 counts (the extra slot is 0 and
-        //    receives the tile total); thread t owns [t*per, t*per + per).
-        //    Waves that own no bin (C2: waves 5-7 of 8) skip it: nobody
-        //    reads their wave sums, which come after every live bin.
-        const bool scan_wave = wave * 64 * per <= nb;  // uniform per wave
+        // 2. exclusive scan of the nbins+1 counts, the run table's column
         uint32_t local[kScanPer];  // 4 * count of bin b
-        uint32_t tsum = 0, incl = 0;
-        if (scan_wave) {
-#pragma unroll
-            for (int q = 0; q < kScanPer; q++) {
-                const int b = tid * per + q;
-                local[q] = (q < per && b <= nb) ? s_hist[b] - ((uint32_t)b << kBinShift) : 0u;
-                tsum += local[q];
-            }
-            incl = wave_incl_scan(tsum);
-            if (lane == 63) s_wsum[wave] = incl;
-        }
+        uint32_t tsum, incl;
+        scan_counts(0u, local, tsum, incl);
         lds_barrier();
-        if (scan_wave) {
-            uint32_t run = incl - tsum;
-            for (int w = 0; w < wave; w++) run += s_wsum[w];
-#pragma unroll
-            for (int q = 0; q < kScanPer; q++) {
-                const int b = tid * per + q;
-                if (q < per && b <= nb) {
-                    // biased by -(b << kBinShift): bin + rank value = byte slot
-                    s_hist[b] = run - ((uint32_t)b << kBinShift);
-                    // segment b's run of this tile, [start, end) in entries,
-                    // packed start | end << 16 (both < 3 * 8192), straight
-                    // from the scan's registers: segment-major column or
-                    // tile-major row
-                    const uint32_t pk = (run >> 2) | (((run + local[q]) >> 2) << 16);
-                    if (b < nb) {
-                        if constexpr (COLS) runs[(size_t)b * ntiles + tile] = pk;
-                        else runs[tile * (size_t)nb + b] = pk;
-                    }
-                    run += local[q];
-                }
-            }
-        }
+        scan_offsets(0u, tile, local, tsum, incl);
         lds_barrier_prio<kPrioAtScan>();
         if (next < ntiles) load_tile_keys<LAYOUT, TB>(ks, next, tid, knext);
         if constexpr (ABL == 3) {
@@ -460,7 +481,165 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
         if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= TB / 2) __builtin_amdgcn_s_setprio(kPrioLevel);
     }
     load_tile_keys<LAYOUT, TB>(ks, tile, tid, kcur);
-    if constexpr (!DEFER) {
+    if constexpr (PIPE != 0) {
+        // The software-pipelined loop.  The scatter is LDS work with almost
+        // no VALU work and the hashing the reverse, so a tile is not
+        // scattered between barriers of its own: tile i-1 is scattered inside
+        // the hash phase of tile i, key slot by key slot.  Two histograms
+        // alternate, H[0] at word 0 of s_hist and H[1] at word kHist: tile i
+        // ranks into H[i & 1].
+        //   phase A (the hash phase's priority), per key slot j: tile i-1's
+        //     three positions of slot j to the image (offsets from
+        //     H[(i-1) & 1]), then tile i's key j hashed, its rank atomics on
+        //     H[i & 1], their results into the same six registers;
+        //   barrier 1: tile i-1's image and tile i's counts are complete;
+        //   phase B (priority 0): scan of H[i & 1] and the run table (with
+        //     its wave-sum barrier), H[(i+1) & 1] biased for tile i+1, the
+        //     next keys loaded, tile i-1 packed and stored;
+        //   final barrier.
+        // Three barriers per tile instead of five.  The block's first tile is
+        // peeled (nothing to scatter), and its last is scattered and written
+        // out in an epilogue.  Only a block's last tile can be short, so a
+        // scatter inside phase A is always of a FULL tile.
+        // One loop body serves both histograms: bin b of the histogram at
+        // word hoff is biased by (hoff + b) << kBinShift, so a rank value
+        // >> 17 is the byte address of its bin's offset in either (the
+        // scatter needs no parity), and the rank atomic's address is one
+        // v_lshl_add of the uniform hoff.  (Two bodies with compile-time
+        // addresses spilled every rank and entry of one of them.)
+        // Ordering:
+        //   - H[(i-1) & 1] is read by the scatters of phase A until barrier 1
+        //     of iteration i and biased again only after that barrier;
+        //     H[i & 1] gets its offsets in phase B, before the final barrier,
+        //     and is read from the next phase A on;
+        //   - s_sorted is written only in phase A (and the epilogue's
+        //     scatter) and read only in phase B (and the epilogue's
+        //     write-out); the final barrier waits for lgkmcnt(0), so the
+        //     packing's reads are done before the next phase A writes.
+        static_assert(!DEFER && !SLOTS && (PRIO == 0 || kPrioMode == kPrioHash),
+                      "PIPE: a build's loop; phase A holds the hash phase's priority");
+        constexpr uint32_t kHist = kMaxB + 1;  // H[1]'s word offset
+        static_assert(((uint64_t)(2 * kHist - 1) << kBinShift) < (1ull << 32), "both histograms' bins in the rank field");
+        uint32_t br[kPartKPT * 3];   // (hoff + segment << kBinShift) + 4 * rank
+        uint32_t ent[kPartKPT * 3];  // low kEntryBits bits of the position
+        constexpr bool kScatters = ABL == 0 || ABL >= 4;
+        // key slot j's three positions into the image
+        auto scatter_key = [&](int j, bool alive) {
+            const char *hist_b = reinterpret_cast<const char *>(s_hist);
+            char *sorted_b = reinterpret_cast<char *>(s_sorted);
+            uint32_t slot[3];  // byte offset in the sorted image
+#pragma unroll
+            for (int h = 0; h < 3; h++)
+                slot[h] = *reinterpret_cast<const uint32_t *>(hist_b + (br[3 * j + h] >> 17)) + br[3 * j + h];
+            if (alive) {
+#pragma unroll
+                for (int h = 0; h < 3; h++) *reinterpret_cast<uint32_t *>(sorted_b + slot[h]) = ent[3 * j + h];
+            }
+        };
+        // (ablation: a stage's results consumed by one impossible store)
+        auto consume = [&](size_t tile) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int q = 0; q < 3 * kPartKPT; q++) x ^= br[q] + ent[q];
+            if (x == 0x9E3779B9u) reinterpret_cast<uint32_t *>(pos_out)[tile * kTileKeys + tid] = x;
+        };
+        auto consume_image = [&](size_t tile) {
+            if ((s_sorted[tid] ^ br[0]) == 0x9E3779B9u)
+                reinterpret_cast<uint32_t *>(pos_out)[tile * kTileKeys + tid] = br[0];
+        };
+        // Iteration `tile` (ranks into the histogram at word hoff) carrying
+        // the scatter and the write-out of tile `prev` (PREV; always FULL).
+        auto pipe_tile = [&](auto full_c, auto prev_c, size_t tile, size_t next, size_t prev, uint32_t hoff) {
+            constexpr bool FULL = decltype(full_c)::value, PREV = decltype(prev_c)::value;
+            const int tile_keys = FULL ? (int)kTileKeys : (int)min((size_t)kTileKeys, ks.n - tile * kTileKeys);
+            auto live = [&](int j) { return FULL || kPartKPT * tid + j < tile_keys; };
+            // phase A
+#pragma unroll
+            for (int j = 0; j < kPartKPT; j++) {
+                if constexpr (PREV && kScatters) scatter_key(j, true);
+                if (live(j)) {
+                    const int32_t k = kcur[j];
+#pragma unroll
+                    for (int h = 0; h < 3; h++) {
+                        const uint64_t raw = h == 0 ? raw_hash1(k) : h == 1 ? raw_hash2(k) : raw_hash3(k);
+                        uint32_t b, e;
+                        bin_entry<MK, MINW>(raw, mp, sm, b, e);
+                        ent[3 * j + h] = e;
+                        if constexpr (ABL == 1) br[3 * j + h] = b;
+                        else br[3 * j + h] = atomicAdd(&s_hist[hoff + b], 4u);
+                    }
+                } else {
+#pragma unroll
+                    for (int h = 0; h < 3; h++) br[3 * j + h] = ent[3 * j + h] = 0;
+                }
+            }
+            lds_barrier_prio<kPrioAtRank>();  // barrier 1
+            // phase B
+            uint32_t local[kScanPer];  // 4 * count of bin b
+            uint32_t tsum, incl;
+            if constexpr (ABL == 0 || ABL >= 3) scan_counts(hoff, local, tsum, incl);
+            // the other histogram's last readers were phase A's scatters
+            const uint32_t other = kHist - hoff;
+#pragma clang loop unroll(disable) vectorize(disable)
+            for (int b = tid; b <= nb; b += TB) s_hist[other + b] = (other + b) << kBinShift;
+            if constexpr (ABL == 0 || ABL >= 3) {
+                lds_barrier();
+                scan_offsets(hoff, tile, local, tsum, incl);
+            }
+            // after the run-start stores, before the tile's: do_tile's order
+            if (next < ntiles) load_tile_keys<LAYOUT, TB>(ks, next, tid, kcur);
+            if constexpr (ABL >= 1 && ABL <= 3) consume(tile);
+            if constexpr (PREV) {
+                if constexpr (ABL == 4) consume_image(prev);
+                if constexpr (kPacks) {
+#pragma unroll
+                    for (int r = 0; r < kStores; r++) pack_store(BoolC<true>{}, r, prev, kTileKeys);
+                }
+            }
+            lds_barrier_prio<kPrioAtHist>();  // final barrier
+        };
+        // Epilogue: the block's last tile scattered, then written out.
+        auto pipe_last = [&](auto full_c, size_t tile) {
+            constexpr bool FULL = decltype(full_c)::value;
+            const int tile_keys = FULL ? (int)kTileKeys : (int)min((size_t)kTileKeys, ks.n - tile * kTileKeys);
+            if constexpr (kScatters) {
+#pragma unroll
+                for (int j = 0; j < kPartKPT; j++) scatter_key(j, FULL || kPartKPT * tid + j < tile_keys);
+                lds_barrier_prio<kPrioAtRank>();
+                if constexpr (ABL == 4) consume_image(tile);
+            }
+            if constexpr (kPacks) {
+#pragma unroll
+                for (int r = 0; r < kStores; r++) pack_store(full_c, r, tile, tile_keys);
+            }
+        };
+
+#pragma clang loop unroll(disable) vectorize(disable)
+        for (int b = tid; b <= nb; b += TB) s_hist[b] = (uint32_t)b << kBinShift;
+        lds_barrier_prio<kPrioAtHist>();
+        if (tile >= nfull) {  // the block's only tile is the short one
+            pipe_tile(BoolC<false>{}, BoolC<false>{}, tile, ntiles, tile, 0u);
+            pipe_last(BoolC<false>{}, tile);
+            return;
+        }
+        size_t prev = tile, next = part_tile(1, ntiles);
+        pipe_tile(BoolC<true>{}, BoolC<false>{}, tile, next, tile, 0u);
+        tile = next;
+        uint32_t hoff = kHist;
+        for (size_t round = 2; tile < nfull; round++) {
+            next = part_tile(round, ntiles);
+            pipe_tile(BoolC<true>{}, BoolC<true>{}, tile, next, prev, hoff);
+            prev = tile;
+            tile = next;
+            hoff = kHist - hoff;
+        }
+        if (tile < ntiles) {
+            pipe_tile(BoolC<false>{}, BoolC<true>{}, tile, ntiles, prev, hoff);
+            pipe_last(BoolC<false>{}, tile);
+        } else {
+            pipe_last(BoolC<true>{}, prev);
+        }
+    } else if constexpr (!DEFER) {
         for (size_t round = 0; tile < nfull; round++) {
             const size_t next = part_tile(round + 1, ntiles);
             do_tile(BoolC<true>{}, BoolC<false>{}, tile, next, tile);
@@ -849,6 +1028,7 @@ struct Pass1Kernel {
     bool defer;      // DEFER: a tile's write-out inside the next tile's hash phase
     unsigned grid;   // persistent workgroups
     int prio;        // PRIO: the phases' issue priority (pass1_prio_of), 0 = none
+    int pipe;        // PIPE: a tile scattered inside the next tile's hash phase, 0 = the plain loop
 };
 // pass 1: the unit of each family launches the kernel p names; false when it
 // holds no such kernel.  Build / probe (slots) at 512 or 1024 threads
@@ -924,6 +1104,24 @@ constexpr int pass1_prio(int threads, bool slots, int wgs_per_cu) {
     return threads == 512 && !slots && wgs_per_cu == 3 ? pass1_prio_of(kPrioHash, 1) : 0;
 }
 
+// The software-pipelined tile loop (k_part_bin's PIPE), in the family that got
+// the hash-phase priority, the 512-thread builds on three workgroups per CU
+// (packed and entry_t keys): on the one-member ladder (kModLadder0,
+// kModLadder0R), whose pipelined kernels keep to 80 VGPRs with 0-6 spilled.
+// C2's pass 1 49.1 -> 46.5 us, the C2 build 0.0818 -> 0.0786 ms in both
+// orders, every run of it below the parent's fastest; from entry_t keys the
+// build is level (0.4226 / 0.4225 ms, 0.4214 / 0.4232).  Not on the general
+// and p2 remainders: their longer hashing spills 22-26 VGPRs around the 48
+// ranks and entries the loop keeps live through every phase, and the general
+// build (m = 100,000,007) measured 0.379 -> 0.418 ms; the p2 form, with the
+// same spills, was not measured.  Not built for the slot-plane kernels, the
+// two-workgroup 512-thread kernels (strided keys, m >= 2^32) and the
+// 1024-thread builds.  (profiles/pass1_scatter_overlap/README.md;
+// tools/ubench.py p1ab_pipe, p1abl pipe; tools/build_ab.py c2, c2e, gen.)
+constexpr int pass1_pipe(int threads, bool slots, int wgs_per_cu, int mk) {
+    return threads == 512 && !slots && wgs_per_cu == 3 && (mk == kModLadder0 || mk == kModLadder0R) ? 1 : 0;
+}
+
 // builds whose sorted tiles exceed the Infinity Cache (C5): stored
 // non-temporal (k_part_bin's NT); compiled for the 1024-thread builds at
 // MAXB 1023 alone
@@ -996,6 +1194,7 @@ inline bool choose_pass1_kernel(const KeySpan &ks, const ModParams &mp, const Pa
     p.nt = !p.super && pass1_may_nt(p.threads, slots, p.maxb) &&
            ws.ntiles * (uint64_t)(p.threads * kPartKPT) * 8 > kInfinityCacheBytes;
     p.prio = p.super ? 0 : pass1_prio(p.threads, slots, p.wgs_per_cu);
+    p.pipe = p.super ? 0 : pass1_pipe(p.threads, slots, p.wgs_per_cu, p.mk);
     p.cols = runs_as_columns(ws);
     p.grid = pass1_grid(ws.ntiles, ncu, p.wgs_per_cu);
     *out = p;
@@ -1024,10 +1223,11 @@ bool launch_pass1_tile(const Pass1Kernel &p, const KeySpan &ks, const ModParams 
                     constexpr int kMinW = pass1_min_waves(TB, kWgs);
                     constexpr bool kMayNT = pass1_may_nt(TB, SLOTS, MAXB);
                     constexpr int kPrio = pass1_prio(TB, SLOTS, kWgs);
-                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT) || p.prio != kPrio) return false;
+                    constexpr int kPipe = pass1_pipe(TB, SLOTS, kWgs, MK);
+                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT) || p.prio != kPrio || p.pipe != kPipe) return false;
                     auto go = [&](auto cols_c, auto nt_c) {
                         k_part_bin<L, SLOTS, decltype(cols_c)::value, TB, MK, MAXB, kMinW, 0,
-                                   decltype(nt_c)::value, kDefer, kPrio>
+                                   decltype(nt_c)::value, kDefer, kPrio, kPipe>
                             <<<p.grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
                     };
                     if constexpr (kMayNT) {

@@ -404,6 +404,17 @@ extern "C" int ubench_pass1_prio(size_t n, uint64_t m, int slots, size_t stride,
     return 0;
 }
 
+// Whether that kernel runs the software-pipelined tile loop
+// (Pass1Kernel::pipe; 0 = the plain loop), same arguments and status.
+extern "C" int ubench_pass1_pipe(size_t n, uint64_t m, int slots, size_t stride, int cu_count,
+                                 int *pipe_out) {
+    Pass1Kernel p{};
+    const int rc = pass1_choice_of(n, m, slots, stride, cu_count, &p);
+    if (rc) return rc;
+    *pipe_out = p.pipe;
+    return 0;
+}
+
 // The product's pass 1, then pass 2 on a forced group walk (CHAINS, VECS,
 // REDIR) at G = 4, in the geometry's own mode and tile size: the four group
 // walks are right at any run length, only their speed differs
@@ -571,6 +582,26 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
         UB_PRIO(pass1_prio_of(kPrioHash, 3), 0) UB_PRIO(pass1_prio_of(kPrioYoung, 1), 0)
 #undef UB_PRIO_LADDER
 #undef UB_PRIO
+        // 5500 + ABL: C2's pass 1 on the software-pipelined tile loop
+        // (k_part_bin's PIPE, the hash phase at priority 1) cut after a
+        // stage; the plain loop's ladder beside it is 5101, 5102, then
+        // 5290 + ABL (PRIO 9)
+#define UB_PIPE(A)                                                                                \
+    case 5500 + A: {                                                                             \
+        SegMap sm{};                                                                             \
+        if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 ||           \
+            ws.nbins > 511 || !runs_as_columns(ws))                                              \
+            return -22;                                                                          \
+        constexpr int kWgs = pass1_wgs_per_cu(512, false, 511);                                  \
+        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), A, false, false, \
+                   pass1_prio_of(kPrioHash, 1), 1>                                               \
+            <<<pass1_grid(ws.ntiles, device_cu_count(), kWgs), 512, 0, s>>>(                     \
+                ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);                          \
+        e = hipGetLastError();                                                                   \
+        break;                                                                                   \
+    }
+        UB_PIPE(0) UB_PIPE(1) UB_PIPE(2) UB_PIPE(3) UB_PIPE(4) UB_PIPE(5)
+#undef UB_PIPE
         // 5413: the 1024-thread builds' pass 1 (one workgroup per CU, write-out
         // deferred) with waves 8-15 at a static priority 1: C5 (one-member
         // ladder, 512 bins, non-temporal tiles) and the f = 10 tree's level-2

@@ -123,7 +123,9 @@ def p1_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50, m=None):
     The priority variants of C2's pass 1 are 5200 + 10 * PRIO (k_part_bin's
     PRIO: 1-3 the sort phases at that level, 5 scatter + packing at 1, 9 the
     hash phase at 1, 13 waves 4-7 at a static 1); 5413 is the static form on
-    the 1024-thread builds (p1ab_c5, p1ab_f10)."""
+    the 1024-thread builds (p1ab_c5, p1ab_f10).  p1ab_pipe: C2's plain loop
+    with the hash phase at priority 1 (5290) against the software-pipelined
+    loop (5500, k_part_bin's PIPE), whichever of them the product runs."""
     run, words, geo = _part_setup(n, bpe, m)
     assert run(0) == 0 and run(1) == 0
     torch.cuda.synchronize()
@@ -213,6 +215,43 @@ def p1_ablation(n=16_777_216, bpe=10.0, rounds=3, reps=50, prios=()):
              0: "product pass 1"}
     for p in prios:
         names.update({5200 + 10 * p + a: f"PRIO {p}: {names[5100 + a]}" for a in (3, 4, 5, 0)})
+    _prewarm(run, 0)
+    res = {v: [] for v in names}
+    for _ in range(rounds):
+        for v in names:
+            assert run(v) == 0
+            res[v].append(round(_events(lambda: run(v), reps) * 1e3, 2))
+    for v, ts in res.items():
+        print(json.dumps({"op": "pass 1 ablation", **geo, "variant": v, "stage": names[v], "us": ts,
+                          "min_us": min(ts)}), flush=True)
+
+
+def p1_ablation_pipe(n=16_777_216, bpe=10.0, rounds=3, reps=50):
+    """C2's pass 1 cut after each stage on both tile loops, the hash phase at
+    priority 1 in both, in the same interleaved rounds.  The plain loop
+    (k_part_bin's ABL at PRIO 9: 5101, 5102 end before the first priority
+    flip, then 5293, 5294, 5295, 5290): 1 hash + bin/entry, 2 + rank atomics,
+    3 + scan and run table, 4 + scatter, 5 + packing, 0 whole.  The
+    pipelined loop (5500 + ABL): the same cuts, where 3 is the scan with no
+    scatter anywhere and 4 adds the scatter interleaved with the next
+    tile's hashing.  5290 and 5500 must give the product's bitmap."""
+    run, words, geo = _part_setup(n, bpe)
+    assert run(0) == 0 and run(1) == 0
+    torch.cuda.synchronize()
+    ref = words.clone()
+    for v in (5290, 5500):
+        words.zero_()
+        assert run(v) == 0 and run(1) == 0
+        torch.cuda.synchronize()
+        print(json.dumps({"check": f"ablation variant {v} bitmap == product",
+                          "ok": bool(torch.equal(ref, words))}), flush=True)
+    stages = {1: "hash + bin/entry", 2: "+ rank atomics", 3: "+ scan, run table", 4: "+ scatter",
+              5: "+ packing (no stores)", 0: "whole pass 1"}
+    names = {}
+    for a, nm in stages.items():
+        names[(5100 if a in (1, 2) else 5290) + a] = "plain loop: " + nm
+        names[5500 + a] = "pipelined loop: " + nm
+    names[0] = "product pass 1"
     _prewarm(run, 0)
     res = {v: [] for v in names}
     for _ in range(rounds):
@@ -583,6 +622,10 @@ def main():
                 print(json.dumps({"op": "lds_or idle lanes", "variant": v, "mode": nm, "round": rnd,
                                   "ms": round(ms, 4)}), flush=True)
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "p1ab_pipe":
+        return p1_ab([5290, 5500])
+    if len(sys.argv) > 1 and sys.argv[1] == "p1abl" and sys.argv[2:3] == ["pipe"]:
+        return p1_ablation_pipe()
     if len(sys.argv) > 1 and sys.argv[1] == "p1abl":
         return p1_ablation(prios=tuple(int(p) for p in sys.argv[2].split(",")) if len(sys.argv) > 2 else ())
     if len(sys.argv) > 1 and sys.argv[1] == "p1ab_c5":
