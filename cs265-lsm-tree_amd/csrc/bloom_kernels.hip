@@ -35,6 +35,7 @@
 #include "bloom_pass1.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 namespace bloomhip {
 
@@ -807,7 +808,12 @@ hipError_t launch_runs_transpose(const PartitionWorkspace &ws, hipStream_t strea
     return hipGetLastError();
 }
 
+// BLOOMHIP_RUN_TABLE = rows | cols forces the layout (read on every call: the
+// tests switch it inside one process); unset or anything else keeps the rule.
 bool runs_as_columns(const PartitionWorkspace &ws) {
+    const char *e = getenv("BLOOMHIP_RUN_TABLE");
+    if (e && !strcmp(e, "rows")) return false;
+    if (e && !strcmp(e, "cols")) return true;
     return ws.ntiles * ws.nbins * 4 <= kColumnTableMaxBytes;
 }
 

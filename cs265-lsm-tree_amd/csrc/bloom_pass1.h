@@ -1001,6 +1001,12 @@ __global__ void __launch_bounds__(kSuperBlock, 4) k_part_bin2(KeySpan ks, ModPar
 // (4 MiB) that costs ~2 us against ~6 us for a transpose launch.  Large ones
 // go through the transpose: at C4 (805 MB) the column stores cost ~2.1 ms
 // (partial-line write-backs), the transpose 0.39 ms (tools/ubench.py part*).
+// The environment variable BLOOMHIP_RUN_TABLE = rows | cols forces one layout
+// at any size (runs_as_columns reads it on every call; unset or any other
+// value keeps the threshold).  Both are right at any size: partition_buffers
+// allocates both tables and launch_bin transposes whenever the table went out
+// as rows.  tests/test_gpu_run_table.py runs the rows kernels and the
+// transpose at small shapes with it.
 // ---------------------------------------------------------------------------
 constexpr size_t kColumnTableMaxBytes = 16u << 20;  // larger run tables: rows + transpose
 constexpr int kTransposeTile = 64;

@@ -325,6 +325,29 @@ bool build_plan(size_t n, uint64_t m, int ncu, PartitionWorkspace *ws, int *mode
     *mode = ws->lad_u ? kApplyBuildL : kApplyBuild;
     return true;
 }
+
+// The product's geometry of a stacked probe of n keys against nf > 1 filters
+// of ms[] bits (largest first for a ladder) on a device of ncu CUs, as
+// probe_stacks plans it: plan_ladder, else plan_stack, tiles as
+// partition_buffers sizes them.  *mmax: the largest member; *mode: the
+// probe's pass-2 mode.
+bool stack_plan(size_t n, int nf, const uint64_t *ms, int ncu, PartitionWorkspace *ws,
+                uint64_t *mmax, int *mode) {
+    StackTable st{};
+    uint64_t g = 0, mmin = ~0ull;
+    *mmax = 0;
+    for (int j = 0; j < nf; j++) {
+        *mmax = std::max(*mmax, ms[j]);
+        mmin = std::min(mmin, ms[j]);
+        g = std::gcd(g, ms[j]);
+    }
+    const bool ladder = plan_ladder(ms, nf, ncu, &st, ws);
+    if (!ladder && !plan_stack(*mmax, g, mmin, nf, ncu, ws)) return false;
+    if (!ws->tile_keys) ws->tile_keys = choose_tile_keys(ws->nbins);
+    ws->ntiles = (n + ws->tile_keys - 1) / ws->tile_keys;
+    *mode = ladder ? kApplyLadder : kApplyStack;
+    return true;
+}
 }  // namespace
 
 // The pass-2 walk the product chooses (choose_apply_walk) on a device of
@@ -338,18 +361,8 @@ extern "C" int ubench_walk_choice(size_t n, int nf, const uint64_t *ms, int cu_c
     if (nf == 1) {
         if (!build_plan(n, ms[0], cu_count, &ws, &mode)) return -34;
     } else {
-        StackTable st{};
-        uint64_t mmax = 0, g = 0, mmin = ~0ull;
-        for (int j = 0; j < nf; j++) {
-            mmax = std::max(mmax, ms[j]);
-            mmin = std::min(mmin, ms[j]);
-            g = std::gcd(g, ms[j]);
-        }
-        const bool ladder = plan_ladder(ms, nf, cu_count, &st, &ws);
-        if (!ladder && !plan_stack(mmax, g, mmin, nf, cu_count, &ws)) return -34;
-        if (!ws.tile_keys) ws.tile_keys = choose_tile_keys(ws.nbins);
-        ws.ntiles = (n + ws.tile_keys - 1) / ws.tile_keys;
-        mode = ladder ? kApplyLadder : kApplyStack;
+        uint64_t mmax = 0;
+        if (!stack_plan(n, nf, ms, cu_count, &ws, &mmax, &mode)) return -34;
     }
     const ApplyWalk w = choose_apply_walk(mode, ws.tile_keys, ws.nbins, ws.ntiles);
     const int out[7] = {mode, (int)ws.tile_keys, (int)ws.nbins, w.g, w.chains, w.vecs, (int)w.redir};
@@ -391,6 +404,40 @@ extern "C" int ubench_pass1_choice(size_t n, uint64_t m, int slots, size_t strid
                          p.nt, p.defer, (int)p.grid};
     std::copy(out, out + 11, out11);
     return 0;
+}
+
+// The same for pass 1 of a stacked probe (slots) of n keys against nf > 1
+// filters of ms[] bits, planned as ubench_walk_choice plans it; no device
+// call.  out11 as above.
+extern "C" int ubench_stack_pass1_choice(size_t n, int nf, const uint64_t *ms, size_t stride,
+                                         int cu_count, int *out11) {
+    if (nf < 2) return -22;
+    PartitionWorkspace ws{};
+    uint64_t mmax = 0;
+    int mode = 0;
+    if (!stack_plan(n, nf, ms, cu_count, &ws, &mmax, &mode)) return -34;
+    const KeySpan ks{nullptr, n, stride, stride == 4 ? KEYS_PACKED : stride == 8 ? KEYS_ENTRY : KEYS_STRIDED};
+    Pass1Kernel p{};
+    SegMap sm{};
+    if (!choose_pass1_kernel(ks, make_mod_params(mmax), ws, true, cu_count, &p, &sm)) return -22;
+    const int out[11] = {p.super, p.threads, p.layout, p.slots, p.cols, p.mk, p.maxb, p.wgs_per_cu,
+                         p.nt, p.defer, (int)p.grid};
+    std::copy(out, out + 11, out11);
+    return 0;
+}
+
+// The product's run-table transpose (launch_runs_transpose, k_runs_transpose)
+// on the caller's device buffers: rows [ntiles][width] -> cols [width][ntiles]
+// (tests/test_gpu_run_table.py checks it against numpy's transpose).
+extern "C" int ubench_runs_transpose(const void *rows, void *cols, size_t ntiles, int width,
+                                     void *stream) {
+    if (!rows || !cols || ntiles == 0 || width <= 0) return -22;
+    PartitionWorkspace ws{};
+    ws.run_rows = const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(rows));
+    ws.run_starts = reinterpret_cast<uint32_t *>(cols);
+    ws.ntiles = ntiles;
+    ws.nbins = (size_t)width;
+    return launch_runs_transpose(ws, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -5;
 }
 
 // The issue priority of that kernel's phases (Pass1Kernel::prio,

@@ -444,3 +444,132 @@ def test_pass2_walk_choice(n, ms, want):
     out = np.zeros(7, dtype=np.int32)
     assert ub.ubench_walk_choice(n, len(ms), sizes.ctypes.data, 256, out.ctypes.data) == 0
     assert tuple(int(x) for x in out) == want
+
+
+# ---------------------------------------------------------------------------
+# The run table's layout (bloom_kernels.hip runs_as_columns): columns while
+# ntiles * nbins * 4 <= kColumnTableMaxBytes (16 MiB), rows and the transpose
+# above; BLOOMHIP_RUN_TABLE = rows | cols forces one, read on every call.
+# ---------------------------------------------------------------------------
+def _with_cols(want, cols):
+    return want[:4] + (cols,) + want[5:]
+
+
+def test_run_table_variable_forces_the_layout(monkeypatch):
+    """rows turns C2's columns into rows, cols turns C4's rows into columns;
+    no other field of the choice moves."""
+    c2, c4 = PASS1_ROWS[0], PASS1_ROWS[4]
+    assert c2[:2] == (16_777_216, 167_772_160) and c2[4][4] == 1
+    assert c4[:2] == (268_435_456, 3 << 30) and c4[4][4] == 0
+    monkeypatch.setenv("BLOOMHIP_RUN_TABLE", "rows")
+    assert _pass1_choice(*c2[:4]) == (0, _with_cols(c2[4], 0))
+    assert _pass1_choice(*c4[:4]) == (0, c4[4])
+    monkeypatch.setenv("BLOOMHIP_RUN_TABLE", "cols")
+    assert _pass1_choice(*c4[:4]) == (0, _with_cols(c4[4], 1))
+    assert _pass1_choice(*c2[:4]) == (0, c2[4])
+    monkeypatch.delenv("BLOOMHIP_RUN_TABLE")
+    assert _pass1_choice(*c2[:4]) == (0, c2[4])
+    assert _pass1_choice(*c4[:4]) == (0, c4[4])
+
+
+@pytest.mark.parametrize("value", [None, "", "columns", "ROWS", "row", "cols ", "0"])
+def test_run_table_variable_unset_or_junk_keeps_the_rule(monkeypatch, value):
+    if value is None:
+        monkeypatch.delenv("BLOOMHIP_RUN_TABLE", raising=False)
+    else:
+        monkeypatch.setenv("BLOOMHIP_RUN_TABLE", value)
+    for n, m, slots, stride, want in PASS1_ROWS:
+        assert _pass1_choice(n, m, slots, stride) == (0, want), (n, m, slots, stride)
+
+
+# Both sides of the threshold on a 256-CU device, per family.  The table is
+# columns while ntiles * segments <= 2^24 / 4, so the most tiles that still
+# give columns are 2^22 // segments, and rows start one key past that many
+# full tiles.  Segments and tile keys are the planners' (WALK_ROWS and the
+# comments of PASS1_ROWS; m = 2^33 - 7: plan_segments takes s = 19 (16,384
+# sub-blocks), 26 rounds of 256 CUs want 6,656 segments, g = 3 sub-blocks
+# exceed the 160 KiB image, so g = 2: 8,192 segments of 2^20 bits, 8192-key
+# tiles as m > 2^32 - 1 sorts no super-tiles), worked out by hand:
+#   8,192 segments: 2^22 // 8192 =    512 tiles x  8192 + 1 =  4,194,305
+#   3,277 segments: 2^22 // 3277 =  1,279 tiles x  8192 + 1 = 10,477,569
+#   3,277 segments on super-tiles:  1,279     x 16,384 + 1 = 20,955,137
+#     256 segments: 2^22 //  256 = 16,384 tiles x  4096 + 1 = 67,108,865
+#     255 segments: 2^22 //  255 = 16,448 tiles x  4096 + 1 = 67,371,009
+#     512 segments: 2^22 //  512 =  8,192 tiles x  8192 + 1 = 67,108,865
+# Rows: (m, slots, segments, tile keys, first n with rows, the choice there).
+RUN_TABLE_THRESHOLDS = [
+    (2**33 - 7, 0, 8192, 8192, 4_194_305, (0, 1024, PACKED, 0, 0, WIDE, 8192, 1, 0, 1, 256)),
+    (2**32, 0, 3277, 8192, 10_477_569, (0, 1024, PACKED, 0, 0, WIDE, 8192, 1, 0, 1, 256)),
+    (2**32 - 1, 0, 3277, 16_384, 20_955_137, (1, 1024, PACKED, 0, 0, FAST, 4095, 1, 0, 0, 256)),
+    # C2's filter: the pipelined 512-thread kernel (ubench_pass1_pipe below)
+    (5 << 25, 0, 256, 4096, 67_108_865, (0, 512, PACKED, 0, 0, LADDER0R, 511, 3, 0, 0, 768)),
+    (100_000_007, 0, 255, 4096, 67_371_009, (0, 512, PACKED, 0, 0, FAST, 511, 3, 0, 0, 768)),
+    # C5's filter: deferred and non-temporal
+    (5 << 27, 0, 512, 8192, 67_108_865, (0, 1024, PACKED, 0, 0, LADDER0R, 1023, 1, 1, 1, 256)),
+    # the one-filter partitioned probe of m = 2^33 - 7
+    (2**33 - 7, 1, 8192, 8192, 4_194_305, (0, 1024, PACKED, 1, 0, WIDE, 8192, 1, 0, 0, 256)),
+]
+
+
+@pytest.mark.parametrize("m,slots,segments,tile,n_rows,want", RUN_TABLE_THRESHOLDS)
+def test_run_table_threshold_both_sides(monkeypatch, m, slots, segments, tile, n_rows, want):
+    monkeypatch.delenv("BLOOMHIP_RUN_TABLE", raising=False)
+    most_column_tiles = (16 << 20) // 4 // segments
+    assert most_column_tiles * segments * 4 <= 16 << 20 < (most_column_tiles + 1) * segments * 4
+    assert n_rows == most_column_tiles * tile + 1
+    assert _pass1_choice(n_rows, m, slots, 4) == (0, want)
+    assert _pass1_choice(n_rows - 1, m, slots, 4) == (0, _with_cols(want, 1))
+
+
+def test_run_table_threshold_pipelined_family(monkeypatch):
+    """The 512-thread build of 5 << 25 past the threshold is the pipelined kernel."""
+    monkeypatch.delenv("BLOOMHIP_RUN_TABLE", raising=False)
+    ub = ctypes.CDLL(os.path.join(os.path.dirname(bh.LIB_PATH), "libbloomhip_ubench.so"))
+    ub.ubench_pass1_pipe.argtypes = [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_size_t,
+                                     ctypes.c_int, ctypes.c_void_p]
+    out = ctypes.c_int(-1)
+    assert ub.ubench_pass1_pipe(67_108_865, 5 << 25, 0, 4, 256, ctypes.byref(out)) == 0
+    assert out.value == 1
+
+
+def _stack_pass1_choice(n, ms, stride=4, cu_count=256):
+    bh.lib()  # torch's HIP runtime first (bloomhip._lib): one runtime per process
+    ub = ctypes.CDLL(os.path.join(os.path.dirname(bh.LIB_PATH), "libbloomhip_ubench.so"))
+    ub.ubench_stack_pass1_choice.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p,
+                                             ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
+    sizes = np.array(ms, dtype=np.uint64)
+    out = np.zeros(11, dtype=np.int32)
+    rc = ub.ubench_stack_pass1_choice(n, len(ms), sizes.ctypes.data, stride, cu_count, out.ctypes.data)
+    return rc, tuple(int(x) for x in out)
+
+
+def test_stack_pass1_kernel_choice(monkeypatch):
+    """Pass 1 of a stacked probe through ubench_stack_pass1_choice, 16.8M GETs
+    on 256 CUs.  The f = 10 tree's three levels: WALK_ROWS' segment stack on
+    1,250 segments of 16,384-key super-tiles, so k_part_bin2 with the slot
+    plane (launch_pass1_super: 1024 threads, the one capacity kSuperMaxBins,
+    one workgroup per CU, 1,024 tiles on 256 persistent workgroups); m_max =
+    512,000,000 = 15,625 << 15 is no p2 form: the general remainder.  C3's
+    five levels: WALK_ROWS' ladder on 256 bins of 8192-key tiles, so the
+    1024-thread k_part_bin with slots on kModLadder at MAXB 1023, neither
+    deferred nor non-temporal with the slot plane.  Both tables (1,024 x
+    1,250 and 2,048 x 256 words) are columns."""
+    monkeypatch.delenv("BLOOMHIP_RUN_TABLE", raising=False)
+    f10 = [5_120_000 * 10**i for i in range(3)]
+    c3 = [655_360 * 4**i for i in range(4, -1, -1)]
+    walk = {tuple(ms): want for _, ms, want in WALK_ROWS}
+    assert walk[tuple(f10[::-1])][:3] == (STACK, 16_384, 1250)
+    assert walk[tuple(c3)][:3] == (LADDER, 8192, 256)
+    want_f10 = (1, 1024, PACKED, 1, 1, FAST, 4095, 1, 0, 0, 256)
+    assert _stack_pass1_choice(16_777_216, f10) == (0, want_f10)
+    assert _stack_pass1_choice(16_777_216, f10[::-1]) == (0, want_f10)
+    want_c3 = (0, 1024, PACKED, 1, 1, 3, 1023, 1, 0, 0, 256)  # mk 3: kModLadder
+    assert _stack_pass1_choice(16_777_216, c3) == (0, want_c3)
+    # entry_t keys, and the variable through this export as well
+    assert _stack_pass1_choice(16_777_216, c3, stride=8) == (0, want_c3[:2] + (ENTRY,) + want_c3[3:])
+    monkeypatch.setenv("BLOOMHIP_RUN_TABLE", "rows")
+    assert _stack_pass1_choice(16_777_216, f10) == (0, _with_cols(want_f10, 0))
+    assert _stack_pass1_choice(16_777_216, c3) == (0, _with_cols(want_c3, 0))
+    # one filter is no stack; sizes with no common segment width have no geometry
+    assert _stack_pass1_choice(1000, [5 << 25])[0] == -22
+    assert _stack_pass1_choice(1000, [1_000_000, 1_000_000])[0] == -34
