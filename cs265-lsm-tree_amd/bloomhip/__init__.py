@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "bloomhip_gen_workload", "bloomhip_set_batch_run", "bloomhip_set_run_meta",
     "bloomhip_get_run_meta", "bloomhip_route_gets", "bloomhip_route_gets_packed", "bloomhip_save", "bloomhip_load",
     "bloomhip_build_from_run_file", "bloomhip_compact", "bloomhip_clone", "bloomhip_get_batch",
+    "bloomhip_range_batch",
 )
 
 
@@ -140,6 +141,8 @@ def _lib():
             "bloomhip_route_gets_packed": (I, [ctypes.POINTER(P), I, P, SZ, SZ, I, P, P, I, P]),
             "bloomhip_get_batch": (I, [ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(SZ), I,
                                        I, P, SZ, SZ, I, P, P, P, I, P]),
+            "bloomhip_range_batch": (I, [ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(SZ), I,
+                                         I, P, P, SZ, I, P, P, SZ, ctypes.POINTER(SZ), I, I, P]),
             "bloomhip_compact": (I, [ctypes.POINTER(P), P, I, I, I, P, ctypes.POINTER(SZ), I, P,
                                      I, P]),
             "bloomhip_save": (I, [P, ctypes.c_char_p]),
@@ -559,6 +562,84 @@ def get_batch(runs: Sequence[BloomFilter], entries, keys, n: int | None = None, 
                                      outs[0][0], outs[1][0], outs[2][0], out_dev,
                                      _stream_ptr(stream)), "bloomhip_get_batch")
     return vals, found_run, stats
+
+
+# bloomhip_range_batch's classes (csrc/bloom_range.h kRangeWaveCap,
+# kRangeBlockCap): a query with at most RANGE_WAVE_CAP candidate entries (the
+# entries of every run inside its bounds) is merged by one wave in LDS, one
+# with at most RANGE_BLOCK_CAP by one workgroup; above that it is a compaction.
+RANGE_WAVE_CAP = 512
+RANGE_BLOCK_CAP = 2048
+
+
+def range_batch(runs, entries, starts, ends, out=None, offsets=None, device=0, stream=None):
+    """Batched RANGE (bloomhip_range_batch): for every query q the entries with
+    starts[q] <= key < ends[q] over all runs, keys ascending, the newest run's
+    entry of a key winning (runs[0] is the newest) and tombstones dropped.
+    runs: BloomFilter handles or None (a run without a handle, such as the
+    memtable, is searched whole); entries[r]: run r's entry_t records (int32
+    [n_r, 2] numpy arrays or device tensors, keys ascending); starts, ends:
+    int32[nq], host or device.  Returns (offsets uint64[nq + 1], out_entries
+    int32[total, 2]): query q's answer is out_entries[offsets[q]:offsets[q + 1]].
+    With no `out`: one count-only call, an exact allocation (on the device when
+    `offsets` is a device tensor), one fill call.  With `out` (int32 [cap, 2],
+    host or device like `offsets`): one call, BloomHipError(ERANGE) when it is
+    too small; the first `total` rows of `out` are returned."""
+    nr = len(runs)
+    if len(entries) != nr:
+        raise ValueError(f"{nr} runs but {len(entries)} entry arrays")
+    for e in entries:  # entry_t {int32 key; int32 val;} (src/types.h:14-22)
+        dt = str(e.dtype)
+        if dt not in ("int32", "torch.int32") or len(e.shape) != 2 or e.shape[1] != 2:
+            raise ValueError(f"entries must be int32 [n, 2] entry_t arrays (got {dt} {tuple(e.shape)})")
+    keeps = [_ptr_of(e) for e in entries]
+    sizes = [_nbytes(k[2]) // 8 for k in keeps]
+    ons = {k[1] for k, sz in zip(keeps, sizes) if sz}  # an empty run has no buffer to place
+    if len(ons) > 1:
+        raise ValueError("entries must be all host or all device buffers")
+    ent_dev = ons.pop() if ons else 0
+    sptr, s_dev, skeep = _keys_ptr(starts, 4)
+    eptr, e_dev, ekeep = _keys_ptr(ends, 4)
+    nq = _nbytes(skeep) // 4
+    if _nbytes(ekeep) // 4 != nq:
+        raise ValueError("starts and ends must have one length")
+    if nq and s_dev != e_dev:
+        raise ValueError("starts and ends must be both host or both device buffers")
+    if offsets is None:
+        if out is not None and _is_tensor(out) and out.is_cuda:
+            import torch
+            offsets = torch.empty(nq + 1, dtype=torch.int64, device=out.device)
+        else:
+            offsets = np.empty(nq + 1, dtype=np.uint64)
+    optr, out_dev, okeep = _out_ptr(offsets, (nq + 1) * 8, 8, "offsets")
+    harr = (ctypes.c_void_p * max(nr, 1))(*[r.handle.value if r is not None else None for r in runs])
+    earr = (ctypes.c_void_p * max(nr, 1))(*[k[0] if sz else None for k, sz in zip(keeps, sizes)])
+    ns = (ctypes.c_size_t * max(nr, 1))(*sizes)
+    total = ctypes.c_size_t()
+
+    def call(buf_ptr, cap):
+        return _lib().bloomhip_range_batch(harr, earr, ns, nr, ent_dev, sptr, eptr, nq, s_dev, optr,
+                                           buf_ptr, cap, ctypes.byref(total), out_dev, device,
+                                           _stream_ptr(stream))
+
+    if out is None:
+        _check(call(None, 0), "bloomhip_range_batch")
+        if out_dev:
+            import torch
+            out = torch.empty((total.value, 2), dtype=torch.int32, device=offsets.device)
+        else:
+            out = np.empty((total.value, 2), dtype=np.int32)
+        if total.value == 0:
+            return offsets, out
+    dt = str(out.dtype)
+    if dt not in ("int32", "torch.int32") or len(out.shape) != 2 or out.shape[1] != 2:
+        raise ValueError(f"out must be an int32 [capacity, 2] entry_t array (got {dt} {tuple(out.shape)})")
+    cap = _nbytes(out) // 8
+    bptr, b_dev, bkeep = _out_ptr(out, 0, 4, "out")
+    if b_dev != out_dev:
+        raise ValueError("offsets and out must be both host or both device buffers")
+    _check(call(bptr if cap else None, cap), "bloomhip_range_batch")
+    return offsets, out[:total.value]
 
 
 def compact(runs, drop_tombstones: bool = False, filter: BloomFilter | None = None,

@@ -24,6 +24,7 @@
 #include "../../include/bloomhip.h"
 #include "bloom_kernels.h"
 #include "bloom_merge.h"
+#include "bloom_range.h"
 
 using namespace bloomhip;
 
@@ -234,7 +235,12 @@ struct Workspace {
     size_t kway_bytes = 0;
     uint32_t *h_kept = nullptr;  // one-pass compaction: kept count, pinned + mapped (coherent)
     uint32_t *d_kept = nullptr;  // its device address
+    // bloomhip_range_batch (RangeBuf): per-call tables, the large queries'
+    // tables, host entries staged, the large queries' slices, host output staged
+    void *rbuf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t rbuf_bytes[5] = {0, 0, 0, 0, 0};
 };
+enum RangeBuf { RBUF_TABLES = 0, RBUF_LARGE = 1, RBUF_ENTRIES = 2, RBUF_SLICES = 3, RBUF_OUT = 4 };
 
 std::mutex g_ws_mu;
 std::map<std::pair<int, hipStream_t>, std::shared_ptr<Workspace>> g_ws;
@@ -271,7 +277,8 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     (void)hipStreamSynchronize(s);
     for (void **p : {(void **)&w->pos, (void **)&w->runs, (void **)&w->res, (void **)&w->slots,
                      &w->mbuf[0], &w->mbuf[1], (void **)&w->msplit, (void **)&w->mcount,
-                     (void **)&w->mkeys, &w->kway}) {
+                     (void **)&w->mkeys, &w->kway, &w->rbuf[0], &w->rbuf[1], &w->rbuf[2], &w->rbuf[3],
+                     &w->rbuf[4]}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -280,6 +287,7 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     w->pos_bytes = w->runs_bytes = w->res_bytes = w->slots_bytes = 0;
     w->mbuf_bytes[0] = w->mbuf_bytes[1] = w->msplit_bytes = w->mcount_bytes = w->mkeys_bytes = 0;
     w->kway_bytes = 0;
+    for (size_t &b : w->rbuf_bytes) b = 0;
 }
 
 hipEvent_t take_event(bloomhip_filter *f) {
@@ -1407,6 +1415,150 @@ int bloomhip_trim(void) {
 
 constexpr uint32_t kKeptPending = 0xFFFFFFFFu;  // never a count: total < 2^32 - 1
 
+}  // extern "C"
+
+namespace {
+
+using RunList = std::vector<std::pair<const char *, uint64_t>>;
+
+// The workspace buffers a compaction of `total` entries in `nruns` runs needs
+// (w locked by the caller), grown before anything is staged into them.
+int compact_reserve(Workspace *w, uint64_t total, int nruns, bool keys_out, hipStream_t s) {
+    // + one entry of padding per run: merge outputs start 16-B aligned
+    const size_t bytes = (std::max<uint64_t>(total, 1) + (uint64_t)nruns + 2) * 8;
+    for (int i = 0; i < 2; i++) HIP_TRY(grow_touched(&w->mbuf[i], &w->mbuf_bytes[i], bytes, s));
+    HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->msplit), &w->msplit_bytes,
+                         merge_split_words(total) * 8, s));
+    HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->mcount), &w->mcount_bytes,
+                         compact_count_words(total) * 4 + 4, s));
+    if (keys_out)
+        HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->mkeys), &w->mkeys_bytes,
+                             std::max<uint64_t>(total, 1) * 4, s));
+    return BLOOMHIP_OK;
+}
+
+// The device part of a compaction (bloomhip_compact, and the large queries of
+// bloomhip_range_batch): `list` = the non-empty runs on the device, newest
+// first, `total` entries in all (< 2^32 - 1; compact_reserve done, w locked).
+// The merged run goes to `out` when given (a device buffer, 16-B aligned when
+// the list is longer than kKwayMaxRuns), else to a workspace buffer; *result
+// is where it is and *kept_out its length, known to the host on return.
+// in_mbuf0: the runs were staged into mbuf[0], which the first merge round
+// must then not write.  f (optional, locked): built from the merged keys.
+int compact_device(Workspace *w, RunList list, uint64_t total, int drop_tombstones, void *out,
+                   bool in_mbuf0, bloomhip_filter *f, hipStream_t s, uint64_t *kept_out,
+                   void **result) {
+    uint64_t kept = 0;
+    if (!list.empty() && list.size() <= (size_t)kKwayMaxRuns) {
+        // one pass: merge + newest-wins dedup + tombstones + packed keys
+        // (bloom_merge.hip k_kway_*), into the caller's buffer or mbuf[1]
+        const void *rp[kKwayMaxRuns];
+        uint64_t rn[kKwayMaxRuns];
+        const int k = (int)list.size();
+        for (int r = 0; r < k; r++) {
+            rp[r] = list[r].first;
+            rn[r] = list[r].second;
+        }
+        HIP_TRY(grow_touched(&w->kway, &w->kway_bytes, kway_workspace_bytes(rn, k), s));
+        if (!w->h_kept) {
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->h_kept), 64,
+                                  hipHostMallocMapped | hipHostMallocCoherent));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&w->d_kept), w->h_kept, 0));
+        }
+        volatile uint32_t *hk = w->h_kept;
+        *hk = kKeptPending;  // overwritten by the merge's last partition
+        void *dst = out ? out : w->mbuf[1];
+        hipError_t e = launch_compact_kway(rp, rn, k, drop_tombstones, dst, f ? w->mkeys : nullptr,
+                                           w->kway, w->d_kept, s);
+        if (e != hipSuccess) return fail_hip(e, "k-way compaction launch");
+        // The kept count sizes the filter build.  The last partition
+        // stores it (system scope) once every kept count before it is
+        // known, while the merge may still be writing entries: the build
+        // is enqueued on the same stream, so it runs after the merge
+        // anyway, and the GPU does not idle through a copy + synchronise
+        // round trip (0.457 ms per bench call with it).  The spin is
+        // bounded (kKeptSpin, with a pause per poll): when the stream has
+        // more queued ahead of the merge than that, the stream is
+        // synchronised instead of holding a core (this also reports a
+        // failed kernel).
+        constexpr std::chrono::microseconds kKeptSpin{2000};
+        const auto t0 = std::chrono::steady_clock::now();
+        while (*hk == kKeptPending && std::chrono::steady_clock::now() - t0 < kKeptSpin)
+            cpu_relax();
+        if (*hk == kKeptPending) HIP_TRY(hipStreamSynchronize(s));
+        kept = *hk;
+        if (kept > total) return fail_hip(hipErrorUnknown, "k-way compaction count not visible");
+        if (f) {
+            int rc = kept ? set_batch_run_locked(f, w->mkeys, (size_t)kept, 4, 1, s, true)
+                          : set_batch_run_locked(f, dst, 0, 8, 1, s, true);
+            if (rc) return rc;
+        }
+        *kept_out = kept;
+        *result = dst;
+        return BLOOMHIP_OK;
+    }
+    // more than kKwayMaxRuns runs: pairwise merge rounds, the left (newer)
+    // input winning ties; round outputs alternate between the two
+    // buffers, never the round's input; then the dedup pass
+    int dst_buf = in_mbuf0 ? 1 : 0;
+    while (list.size() > 1) {
+        RunList next;
+        char *base = static_cast<char *>(w->mbuf[dst_buf]);
+        uint64_t o = 0;
+        // the round's merges go out together (one split + one tile
+        // launch per kMaxMergePairs pairs)
+        std::vector<MergePairArgs> pairs;
+        for (size_t i = 0; i < list.size(); i += 2) {
+            char *dst = base + o * 8;
+            if (i + 1 < list.size()) {
+                pairs.push_back({list[i].first, list[i].second, list[i + 1].first,
+                                 list[i + 1].second, dst});
+                next.push_back({dst, list[i].second + list[i + 1].second});
+            } else {
+                HIP_TRY(hipMemcpyAsync(dst, list[i].first, list[i].second * 8,
+                                       hipMemcpyDeviceToDevice, s));
+                next.push_back({dst, list[i].second});
+            }
+            o += (next.back().second + 1) & ~1ull;  // every output 16-B aligned
+        }
+        for (size_t p0 = 0; p0 < pairs.size(); p0 += kMaxMergePairs) {
+            const int np = (int)std::min<size_t>(kMaxMergePairs, pairs.size() - p0);
+            hipError_t e = launch_merge_round(pairs.data() + p0, np, w->msplit, s);
+            if (e != hipSuccess) return fail_hip(e, "merge launch");
+        }
+        list.swap(next);
+        dst_buf ^= 1;
+    }
+    // newest entry per key, tombstones dropped on request
+    const char *merged = list.empty() ? nullptr : list[0].first;
+    void *dst = out ? out : w->mbuf[merged == w->mbuf[0] ? 1 : 0];
+    if (merged) {
+        // with a filter to build, the kept keys also go out packed: the
+        // build's pass 1 then reads 4 B per key, not the 8-B entries
+        hipError_t e = launch_dedup(merged, total, drop_tombstones, dst, w->mcount, s,
+                                    f ? w->mkeys : nullptr);
+        if (e != hipSuccess) return fail_hip(e, "dedup launch");
+        uint32_t cnt = 0;
+        HIP_TRY(hipMemcpyAsync(&cnt, w->mcount + compact_count_words(total) - 1, 4,
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        kept = cnt;
+    }
+    if (f) {
+        // the merged run is sorted by key: fences and max key directly
+        int rc = kept ? set_batch_run_locked(f, w->mkeys, (size_t)kept, 4, 1, s, true)
+                      : set_batch_run_locked(f, dst, 0, 8, 1, s, true);
+        if (rc) return rc;
+    }
+    *kept_out = kept;
+    *result = dst;
+    return BLOOMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 int bloomhip_compact(const void *const *runs, const size_t *nentries, int nruns,
                      int runs_on_device, int drop_tombstones, void *out_entries, size_t *n_out,
                      int out_on_device, bloomhip_filter *f, int device, void *stream) {
@@ -1433,18 +1585,10 @@ int bloomhip_compact(const void *const *runs, const size_t *nentries, int nruns,
         std::unique_lock<std::mutex> flk;
         if (f) flk = std::unique_lock<std::mutex>(f->mu);
         const LockedWorkspace w(device, s);
-        // + one entry of padding per run: merge outputs start 16-B aligned
-        const size_t bytes = (std::max<uint64_t>(total, 1) + (uint64_t)nruns + 2) * 8;
-        for (int i = 0; i < 2; i++) HIP_TRY(grow_touched(&w->mbuf[i], &w->mbuf_bytes[i], bytes, s));
-        HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->msplit), &w->msplit_bytes,
-                             merge_split_words(total) * 8, s));
-        HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->mcount), &w->mcount_bytes,
-                             compact_count_words(total) * 4 + 4, s));
-        if (f)
-            HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->mkeys), &w->mkeys_bytes,
-                                 std::max<uint64_t>(total, 1) * 4, s));
+        int rc = compact_reserve(w.get(), total, nruns, f != nullptr, s);
+        if (rc) return rc;
         // the runs, newest first; host runs are staged into mbuf[0]
-        std::vector<std::pair<const char *, uint64_t>> list;
+        RunList list;
         uint64_t off = 0;
         for (int r = 0; r < nruns; r++) {
             if (!nentries[r]) continue;
@@ -1457,114 +1601,229 @@ int bloomhip_compact(const void *const *runs, const size_t *nentries, int nruns,
                 off += nentries[r];
             }
         }
-        if (!list.empty() && list.size() <= (size_t)kKwayMaxRuns) {
-            // one pass: merge + newest-wins dedup + tombstones + packed keys
-            // (bloom_merge.hip k_kway_*), into the caller's buffer or mbuf[1]
-            const void *rp[kKwayMaxRuns];
-            uint64_t rn[kKwayMaxRuns];
-            const int k = (int)list.size();
-            for (int r = 0; r < k; r++) {
-                rp[r] = list[r].first;
-                rn[r] = list[r].second;
-            }
-            HIP_TRY(grow_touched(&w->kway, &w->kway_bytes, kway_workspace_bytes(rn, k), s));
-            if (!w->h_kept) {
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&w->h_kept), 64,
-                                      hipHostMallocMapped | hipHostMallocCoherent));
-                HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&w->d_kept), w->h_kept, 0));
-            }
-            volatile uint32_t *hk = w->h_kept;
-            *hk = kKeptPending;  // overwritten by the merge's last partition
-            void *dst = out_on_device ? out_entries : w->mbuf[1];
-            hipError_t e = launch_compact_kway(rp, rn, k, drop_tombstones, dst, f ? w->mkeys : nullptr,
-                                               w->kway, w->d_kept, s);
-            if (e != hipSuccess) return fail_hip(e, "k-way compaction launch");
-            // The kept count sizes the filter build.  The last partition
-            // stores it (system scope) once every kept count before it is
-            // known, while the merge may still be writing entries: the build
-            // is enqueued on the same stream, so it runs after the merge
-            // anyway, and the GPU does not idle through a copy + synchronise
-            // round trip (0.457 ms per bench call with it).  The spin is
-            // bounded (kKeptSpin, with a pause per poll): when the stream has
-            // more queued ahead of the merge than that, the stream is
-            // synchronised instead of holding a core (this also reports a
-            // failed kernel).
-            constexpr std::chrono::microseconds kKeptSpin{2000};
-            const auto t0 = std::chrono::steady_clock::now();
-            while (*hk == kKeptPending && std::chrono::steady_clock::now() - t0 < kKeptSpin)
-                cpu_relax();
-            if (*hk == kKeptPending) HIP_TRY(hipStreamSynchronize(s));
-            kept = *hk;
-            if (kept > total) return fail_hip(hipErrorUnknown, "k-way compaction count not visible");
-            if (f) {
-                int rc = kept ? set_batch_run_locked(f, w->mkeys, (size_t)kept, 4, 1, s, true)
-                              : set_batch_run_locked(f, dst, 0, 8, 1, s, true);
-                if (rc) return rc;
-            }
-            if (!out_on_device && kept)
-                HIP_TRY(hipMemcpyAsync(out_entries, dst, kept * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            *n_out = (size_t)kept;
-            return BLOOMHIP_OK;
-        }
-        // more than kKwayMaxRuns runs: pairwise merge rounds, the left (newer)
-        // input winning ties; round outputs alternate between the two
-        // buffers, never the round's input; then the dedup pass
-        int dst_buf = runs_on_device ? 0 : 1;
-        while (list.size() > 1) {
-            std::vector<std::pair<const char *, uint64_t>> next;
-            char *base = static_cast<char *>(w->mbuf[dst_buf]);
-            uint64_t o = 0;
-            // the round's merges go out together (one split + one tile
-            // launch per kMaxMergePairs pairs)
-            std::vector<MergePairArgs> pairs;
-            for (size_t i = 0; i < list.size(); i += 2) {
-                char *dst = base + o * 8;
-                if (i + 1 < list.size()) {
-                    pairs.push_back({list[i].first, list[i].second, list[i + 1].first,
-                                     list[i + 1].second, dst});
-                    next.push_back({dst, list[i].second + list[i + 1].second});
-                } else {
-                    HIP_TRY(hipMemcpyAsync(dst, list[i].first, list[i].second * 8,
-                                           hipMemcpyDeviceToDevice, s));
-                    next.push_back({dst, list[i].second});
-                }
-                o += (next.back().second + 1) & ~1ull;  // every output 16-B aligned
-            }
-            for (size_t p0 = 0; p0 < pairs.size(); p0 += kMaxMergePairs) {
-                const int np = (int)std::min<size_t>(kMaxMergePairs, pairs.size() - p0);
-                hipError_t e = launch_merge_round(pairs.data() + p0, np, w->msplit, s);
-                if (e != hipSuccess) return fail_hip(e, "merge launch");
-            }
-            list.swap(next);
-            dst_buf ^= 1;
-        }
-        // newest entry per key, tombstones dropped on request
-        const char *merged = list.empty() ? nullptr : list[0].first;
-        void *dst = out_on_device ? out_entries : w->mbuf[merged == w->mbuf[0] ? 1 : 0];
-        if (merged) {
-            // with a filter to build, the kept keys also go out packed: the
-            // build's pass 1 then reads 4 B per key, not the 8-B entries
-            hipError_t e = launch_dedup(merged, total, drop_tombstones, dst, w->mcount, s,
-                                        f ? w->mkeys : nullptr);
-            if (e != hipSuccess) return fail_hip(e, "dedup launch");
-            uint32_t cnt = 0;
-            HIP_TRY(hipMemcpyAsync(&cnt, w->mcount + compact_count_words(total) - 1, 4,
-                                   hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            kept = cnt;
-        }
-        if (f) {
-            // the merged run is sorted by key: fences and max key directly
-            int rc = kept ? set_batch_run_locked(f, w->mkeys, (size_t)kept, 4, 1, s, true)
-                          : set_batch_run_locked(f, dst, 0, 8, 1, s, true);
-            if (rc) return rc;
-        }
+        void *dst = nullptr;
+        rc = compact_device(w.get(), std::move(list), total, drop_tombstones,
+                            out_on_device ? out_entries : nullptr, !runs_on_device, f, s, &kept, &dst);
+        if (rc) return rc;
         if (!out_on_device && kept)
             HIP_TRY(hipMemcpyAsync(out_entries, dst, kept * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
     *n_out = (size_t)kept;
+    return BLOOMHIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// BLOOMHIP_RANGE_PATH = auto | compact, read per call: compact sends every
+// non-empty query down the large path (the tests reach it at small shapes).
+bool range_path_compact() {
+    const char *e = getenv("BLOOMHIP_RANGE_PATH");
+    return e && !strcmp(e, "compact");
+}
+
+size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+int bloomhip_range_batch(const bloomhip_filter *const *runs, const void *const *entries,
+                         const size_t *nentries, int nruns, int entries_on_device,
+                         const int32_t *starts, const int32_t *ends, size_t nq, int bounds_on_device,
+                         uint64_t *offsets, void *out_entries, size_t out_capacity,
+                         size_t *total_out, int out_on_device, int device, void *stream) {
+    g_last_error.clear();
+    if (!runs || !entries || !nentries || nruns <= 0 || nruns > kMaxRouteRuns) return BLOOMHIP_EINVAL;
+    if (!offsets || !total_out || (nq && (!starts || !ends))) return BLOOMHIP_EINVAL;
+    if (!out_entries && out_capacity) return BLOOMHIP_EINVAL;
+    if (out_on_device && (reinterpret_cast<uintptr_t>(offsets) & 7)) return BLOOMHIP_EINVAL;
+    if (out_on_device && (reinterpret_cast<uintptr_t>(out_entries) & 7)) return BLOOMHIP_EINVAL;
+    if (nq >= 0xFFFFFFFFull) return BLOOMHIP_ERANGE;  // the class lists hold u32 query indices
+    size_t total_entries = 0;
+    std::vector<const bloomhip_filter *> handles;
+    for (int j = 0; j < nruns; j++) {
+        if (runs[j] && runs[j]->device != device) return BLOOMHIP_EINVAL;
+        if (nentries[j] && !entries[j]) return BLOOMHIP_EINVAL;
+        // entry_t records are read as 8-byte words on the device
+        if (reinterpret_cast<uintptr_t>(entries[j]) & (entries_on_device ? 7 : 3)) return BLOOMHIP_EINVAL;
+        total_entries += nentries[j];
+        if (runs[j]) handles.push_back(runs[j]);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BLOOMHIP_ENODEV;
+    if (device < 0 || device >= ndev) return BLOOMHIP_EINVAL;
+    DeviceGuard g(device);
+    // filter locks, then the workspace lock: the global lock order
+    HandleLocks locks(handles.data(), (int)handles.size());
+    // A run with fences must have the entries its fences describe, as for
+    // bloomhip_get_batch; a run without them is searched whole.
+    for (int j = 0; j < nruns; j++) {
+        const size_t nf = runs[j] && runs[j]->d_meta ? runs[j]->nfences : 0;
+        if (nf && nf != (nentries[j] + kFenceStride - 1) / kFenceStride) return BLOOMHIP_EINVAL;
+    }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const LockedWorkspace w(device, s);
+    if (nq == 0) {
+        if (out_on_device) {
+            HIP_TRY(hipMemsetAsync(offsets, 0, 8, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        } else {
+            offsets[0] = 0;
+        }
+        *total_out = 0;
+        return BLOOMHIP_OK;
+    }
+    const bool fill = out_entries != nullptr;
+    // the runs on the device
+    RangeRuns R{};
+    R.nruns = nruns;
+    {
+        char *dst = nullptr;
+        if (!entries_on_device) {
+            HIP_TRY(grow(&w->rbuf[RBUF_ENTRIES], &w->rbuf_bytes[RBUF_ENTRIES], total_entries * 8));
+            dst = static_cast<char *>(w->rbuf[RBUF_ENTRIES]);
+        }
+        uint32_t off = 0;
+        for (int j = 0; j < nruns; j++) {
+            R.nentries[j] = nentries[j];
+            if (entries_on_device) {
+                R.entries[j] = entries[j];
+            } else {
+                R.entries[j] = dst;
+                if (nentries[j])
+                    HIP_TRY(hipMemcpyAsync(dst, entries[j], nentries[j] * 8, hipMemcpyHostToDevice, s));
+                dst += nentries[j] * 8;
+            }
+            const bool fenced = runs[j] && runs[j]->d_meta && runs[j]->nfences;
+            R.meta[j] = fenced ? runs[j]->d_meta : nullptr;
+            R.nfences[j] = fenced ? runs[j]->nfences : 0;
+            R.fence_off[j] = off;
+            off += R.nfences[j];
+        }
+        R.total_fences = off;
+    }
+    // per-call tables, carved from one buffer: counts (the offsets-to-be,
+    // unless the caller's are on the device), lo, ub, len, the class lists
+    // and their lengths, the bounds staged from the host
+    const size_t nqr = nq * (size_t)nruns;
+    const size_t b_counts = out_on_device ? 0 : align16((nq + 1) * 8);
+    const size_t b_lo = align16(nqr * 8), b_ub = align16(nq * 8), b_len = align16(nqr * 4);
+    const size_t b_list = align16(nq * 4), b_bounds = bounds_on_device ? 0 : align16(nq * 4);
+    HIP_TRY(grow(&w->rbuf[RBUF_TABLES], &w->rbuf_bytes[RBUF_TABLES],
+                 b_counts + b_lo + b_ub + b_len + 3 * b_list + 16 + 2 * b_bounds));
+    char *t = static_cast<char *>(w->rbuf[RBUF_TABLES]);
+    auto carve = [&](size_t bytes) { char *p = t; t += bytes; return p; };
+    uint64_t *d_counts = out_on_device ? offsets : reinterpret_cast<uint64_t *>(carve(b_counts));
+    uint64_t *d_lo = reinterpret_cast<uint64_t *>(carve(b_lo));
+    uint64_t *d_ub = reinterpret_cast<uint64_t *>(carve(b_ub));
+    uint32_t *d_len = reinterpret_cast<uint32_t *>(carve(b_len));
+    RangeLists L{};
+    for (int c = 0; c < 3; c++) L.list[c] = reinterpret_cast<uint32_t *>(carve(b_list));
+    L.count = reinterpret_cast<uint32_t *>(carve(16));
+    const int32_t *d_starts = starts, *d_ends = ends;
+    if (!bounds_on_device) {
+        int32_t *ds = reinterpret_cast<int32_t *>(carve(b_bounds));
+        int32_t *de = reinterpret_cast<int32_t *>(carve(b_bounds));
+        HIP_TRY(hipMemcpyAsync(ds, starts, nq * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(de, ends, nq * 4, hipMemcpyHostToDevice, s));
+        d_starts = ds;
+        d_ends = de;
+    }
+    HIP_TRY(hipMemsetAsync(L.count, 0, 16, s));
+    // 1. bounds and classes
+    hipError_t e = launch_range_bounds(R, d_starts, d_ends, nq, range_path_compact(), d_lo, d_len, d_ub,
+                                       d_counts, L, s);
+    if (e != hipSuccess) return fail_hip(e, "k_range_bounds launch");
+    uint32_t ncls[4] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(ncls, L.count, 12, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // 2. the count pass of both LDS classes
+    for (int c : {RANGE_WAVE, RANGE_BLOCK}) {
+        e = launch_range_merge(R, c, L.list[c], ncls[c], d_lo, d_len, d_counts, nullptr, s);
+        if (e != hipSuccess) return fail_hip(e, "k_range_merge (count) launch");
+    }
+    // 3. the large queries: each a compaction of its sub-ranges, tombstones
+    // dropped, into its own 16-B-aligned slice (fill) or one reused slice
+    const uint32_t nl = ncls[RANGE_LARGE];
+    uint64_t *d_slice_off = nullptr;
+    if (nl) {
+        const size_t rows = (size_t)nl * (size_t)nruns;
+        const size_t lb_lo = align16(rows * 8), lb_len = align16(rows * 4), lb_q = align16((size_t)nl * 8);
+        HIP_TRY(grow(&w->rbuf[RBUF_LARGE], &w->rbuf_bytes[RBUF_LARGE], lb_lo + lb_len + 3 * lb_q));
+        char *lt = static_cast<char *>(w->rbuf[RBUF_LARGE]);
+        uint64_t *d_lo_rows = reinterpret_cast<uint64_t *>(lt);
+        uint32_t *d_len_rows = reinterpret_cast<uint32_t *>(lt + lb_lo);
+        uint64_t *d_ub_rows = reinterpret_cast<uint64_t *>(lt + lb_lo + lb_len);
+        uint64_t *d_kept = d_ub_rows + lb_q / 8;
+        d_slice_off = d_kept + lb_q / 8;
+        e = launch_range_gather(L.list[RANGE_LARGE], nl, nruns, d_lo, d_len, d_ub, d_lo_rows, d_len_rows,
+                                d_ub_rows, s);
+        if (e != hipSuccess) return fail_hip(e, "k_range_gather launch");
+        std::vector<uint64_t> h_lo(rows), h_ub(nl), h_kept(nl), h_slice(nl);
+        std::vector<uint32_t> h_len(rows);
+        HIP_TRY(hipMemcpyAsync(h_lo.data(), d_lo_rows, rows * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_len.data(), d_len_rows, rows * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(h_ub.data(), d_ub_rows, (size_t)nl * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        uint64_t slices = 0, ub_max = 0;
+        for (uint32_t i = 0; i < nl; i++) {
+            if (h_ub[i] >= 0xFFFFFFFFull) return BLOOMHIP_ERANGE;  // bloomhip_compact's limit
+            h_slice[i] = fill ? slices : 0;
+            slices += (h_ub[i] + 1) & ~1ull;
+            ub_max = std::max(ub_max, h_ub[i]);
+        }
+        HIP_TRY(grow_touched(&w->rbuf[RBUF_SLICES], &w->rbuf_bytes[RBUF_SLICES],
+                             (fill ? slices : ub_max + 1) * 8, s));
+        int rc = compact_reserve(w.get(), ub_max, nruns, false, s);
+        if (rc) return rc;
+        for (uint32_t i = 0; i < nl; i++) {
+            RunList list;
+            for (int r = 0; r < nruns; r++) {
+                const size_t x = (size_t)i * (size_t)nruns + r;
+                if (h_len[x])
+                    list.push_back({static_cast<const char *>(R.entries[r]) + h_lo[x] * 8, h_len[x]});
+            }
+            void *res = nullptr;
+            rc = compact_device(w.get(), std::move(list), h_ub[i], 1,
+                                static_cast<char *>(w->rbuf[RBUF_SLICES]) + h_slice[i] * 8, false, nullptr,
+                                s, &h_kept[i], &res);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(d_kept, h_kept.data(), (size_t)nl * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_slice_off, h_slice.data(), (size_t)nl * 8, hipMemcpyHostToDevice, s));
+        e = launch_range_set_counts(L.list[RANGE_LARGE], nl, d_kept, d_counts, s);
+        if (e != hipSuccess) return fail_hip(e, "k_range_set_counts launch");
+        HIP_TRY(hipStreamSynchronize(s));  // the host vectors leave scope
+    }
+    // 4. counts to offsets
+    e = launch_range_scan(d_counts, nq, s);
+    if (e != hipSuccess) return fail_hip(e, "k_range_scan launch");
+    uint64_t total = 0;
+    if (out_on_device) HIP_TRY(hipMemcpyAsync(&total, d_counts + nq, 8, hipMemcpyDeviceToHost, s));
+    else HIP_TRY(hipMemcpyAsync(offsets, d_counts, (nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!out_on_device) total = offsets[nq];
+    *total_out = (size_t)total;
+    if (!fill) return BLOOMHIP_OK;
+    if (total > out_capacity) return BLOOMHIP_ERANGE;
+    if (total == 0) return BLOOMHIP_OK;
+    // 5. the write pass of both LDS classes, and the large queries' copies
+    void *d_out = out_entries;
+    if (!out_on_device) {
+        HIP_TRY(grow(&w->rbuf[RBUF_OUT], &w->rbuf_bytes[RBUF_OUT], total * 8));
+        d_out = w->rbuf[RBUF_OUT];
+    }
+    for (int c : {RANGE_WAVE, RANGE_BLOCK}) {
+        e = launch_range_merge(R, c, L.list[c], ncls[c], d_lo, d_len, d_counts, d_out, s);
+        if (e != hipSuccess) return fail_hip(e, "k_range_merge (write) launch");
+    }
+    e = launch_range_copy_large(L.list[RANGE_LARGE], nl, d_slice_off, d_counts, w->rbuf[RBUF_SLICES], d_out, s);
+    if (e != hipSuccess) return fail_hip(e, "k_range_copy_large launch");
+    if (!out_on_device) HIP_TRY(hipMemcpyAsync(out_entries, d_out, total * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return BLOOMHIP_OK;
 }
 

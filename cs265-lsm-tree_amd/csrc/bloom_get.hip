@@ -18,6 +18,7 @@
 // ENTRIES, :164: 512 entries at the wrong place for every page > 0.  The
 // interval the fences describe is searched here)
 #include "bloom_combine.h"  // route_page
+#include "bloom_search.h"   // halving_search, floor_pow2
 
 #include <algorithm>
 
@@ -32,25 +33,6 @@ constexpr int32_t kGetNone = INT32_MIN;  // vals[i] when no run holds the key (=
 // (one sigma), so +-128 is four sigma, and a wave of 64 lanes takes the exact
 // fallback in under 1 % of its searches.
 constexpr uint32_t kGetWindow = 256;
-
-// Largest power of two <= x (x >= 1).
-__device__ __forceinline__ uint32_t floor_pow2(uint32_t x) { return 1u << (31 - __clz((int)x)); }
-
-// The entry with the largest key <= k among p[pos .. pos + 2 * st0 - 1]
-// (indices clamped below len), given that p[pos].key <= k: a branchless
-// halving search, one dependent 8-byte read per step.  pos leaves as that
-// entry's index and best as the entry; when no step is taken both stay as
-// they came (best = p[pos] is the caller's to supply).
-__device__ __forceinline__ void halving_search(const int2 *__restrict__ p, uint32_t &pos, uint32_t len,
-                                               uint32_t st0, int32_t k, int2 &best) {
-    for (uint32_t st = st0; st; st >>= 1) {
-        const uint32_t c = pos + st;
-        const int2 v = p[min(c, len - 1)];  // clamped: an index past the interval counts as > k
-        const bool take = c < len && v.x <= k;
-        pos = take ? c : pos;
-        best = take ? v : best;
-    }
-}
 
 // One wave handles 64 consecutive keys per step, fetched one step ahead with
 // the step's candidate words (lane r < nruns loads run r's word), as k_route

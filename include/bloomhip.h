@@ -250,6 +250,60 @@ int bloomhip_compact(const void *const *runs, const size_t *nentries, int nruns,
                      int runs_on_device, int drop_tombstones, void *out_entries, size_t *n_out,
                      int out_on_device, bloomhip_filter *f, int device, void *stream);
 
+/* --- batched RANGE: newest-wins range scans over the runs -------------------
+ * LSMTree::range (src/lsm_tree.cpp:218-290) over Buffer::range and Run::range
+ * (src/run.cpp:115-157), for nq queries at once.  Query q has the bounds
+ * [starts[q], ends[q]), end exclusive as the reference's CLI.  Its answer is
+ * the entries {key, val} with starts[q] <= key < ends[q], taken over all runs,
+ * keys ascending; for a key held by several runs only the newest run's entry
+ * counts (runs[0] is the newest), and that entry is dropped when its value is
+ * VAL_TOMBSTONE (INT32_MIN): a tombstone in a newer run hides older live
+ * values (src/lsm_tree.cpp:273-279; MergeContext precedence, src/merge.cpp).
+ * ends[q] <= starts[q] answers nothing (:226-229); a key equal to INT32_MAX is
+ * never returned, as in the reference.
+ * The answer depends only on entries, starts and ends; run metadata only
+ * speeds the search.  1 <= nruns <= 64.  runs[r] may be NULL or a handle
+ * without metadata: that run is searched by plain binary search over its
+ * entries, which is how the memtable (Buffer::range) is passed, as a sorted
+ * runs[0].  Every non-NULL handle is on `device`; one that has fences must
+ * have nfences == ceil(nentries[r] / 4096), as for bloomhip_get_batch.
+ * entries[r]: entry_t records, keys strictly ascending, on `device` when
+ * entries_on_device (8-byte aligned); host entries are staged inside the call.
+ * starts, ends: packed int32[nq], on the device when bounds_on_device.
+ * Outputs: offsets (required, nq + 1 u64) and out_entries, both host or both
+ * device (out_on_device; 8-byte aligned there): query q's answer is
+ * out_entries[offsets[q] .. offsets[q + 1]), offsets[0] = 0 and offsets[nq] =
+ * *total_out (required, a host pointer).
+ *   out_entries == NULL && out_capacity == 0: count only; offsets and
+ *     *total_out are filled, BLOOMHIP_OK.
+ *   *total_out > out_capacity otherwise: BLOOMHIP_ERANGE; offsets and
+ *     *total_out are valid and no byte of out_entries is written.
+ *   nq == 0: offsets[0] = 0, *total_out = 0.
+ * Always synchronous (the total is returned).
+ * BLOOMHIP_EINVAL (nothing is launched): NULLs where data is required,
+ * nentries[r] > 0 with entries[r] NULL, misaligned entries or device outputs,
+ * a fence / entry mismatch, a handle on another device, nruns out of range, a
+ * bad device.  BLOOMHIP_ERANGE also for nq >= 2^32 - 1, and for a query with
+ * more than BLOOMHIP's compaction limit of candidates (2^32 - 2 entries of
+ * all runs inside its bounds), which is answered as a compaction of its
+ * sub-ranges; offsets are not valid then.  Every entry index is clamped into
+ * [0, nentries[r]]: entries that disagree with their fences, or are not
+ * strictly ascending, give unspecified answers but no access outside them or
+ * outside the query's slice of out_entries.
+ * BLOOMHIP_RANGE_PATH = auto | compact (environment, read per call): compact
+ * answers every non-empty query as a compaction (for tests).
+ * Deviation from the reference, beside the one of bloomhip_get_batch:
+ * Run::range maps num_pages * 4096 BYTES at byte offset page * 4096
+ * (src/run.cpp:142-145) while the fences sit every 4096 ENTRIES (:164), so
+ * for runs over 512 entries it scans the wrong place.  Here every entry of
+ * the run inside the bounds is returned; for runs of at most 512 entries the
+ * two agree. */
+int bloomhip_range_batch(const bloomhip_filter *const *runs, const void *const *entries,
+                         const size_t *nentries, int nruns, int entries_on_device,
+                         const int32_t *starts, const int32_t *ends, size_t nq, int bounds_on_device,
+                         uint64_t *offsets, void *out_entries, size_t out_capacity,
+                         size_t *total_out, int out_on_device, int device, void *stream);
+
 /* Scalar compatibility entry points (one key; synchronous), for
  * BloomFilter::set (src/bloom_filter.cpp:49-53) and is_set (:55-59) called
  * once per key.  Low-latency path: the key travels as a kernel argument (no
