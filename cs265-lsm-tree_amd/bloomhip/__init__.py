@@ -62,7 +62,7 @@ EXPORTED_SYMBOLS = (
     "bloomhip_gen_workload", "bloomhip_set_batch_run", "bloomhip_set_run_meta",
     "bloomhip_get_run_meta", "bloomhip_route_gets", "bloomhip_route_gets_packed", "bloomhip_save", "bloomhip_load",
     "bloomhip_build_from_run_file", "bloomhip_compact", "bloomhip_clone", "bloomhip_get_batch",
-    "bloomhip_range_batch",
+    "bloomhip_range_batch", "bloomhip_flush_batch",
 )
 
 
@@ -145,6 +145,7 @@ def _lib():
                                          I, P, P, SZ, I, P, P, SZ, ctypes.POINTER(SZ), I, I, P]),
             "bloomhip_compact": (I, [ctypes.POINTER(P), P, I, I, I, P, ctypes.POINTER(SZ), I, P,
                                      I, P]),
+            "bloomhip_flush_batch": (I, [P, SZ, I, I, P, ctypes.POINTER(SZ), I, P, I, P]),
             "bloomhip_save": (I, [P, ctypes.c_char_p]),
             "bloomhip_clone": (I, [P, I, ctypes.POINTER(P)]),
             "bloomhip_load": (I, [ctypes.c_char_p, I, ctypes.POINTER(P)]),
@@ -671,6 +672,41 @@ def compact(runs, drop_tombstones: bool = False, filter: BloomFilter | None = No
                                    filter.handle if filter is not None else None,
                                    filter.device if filter is not None else device,
                                    _stream_ptr(stream)), "bloomhip_compact")
+    return out[:n_out.value]
+
+
+# bloomhip_flush_batch's geometry (csrc/bloom_flush.h kFlushTile,
+# kFlushBlockCap, kFlushScanChunk): the tiled radix sort ranks FLUSH_TILE ops
+# per workgroup; a batch of at most FLUSH_BLOCK_CAP ops is sorted by one
+# workgroup in one launch; the [digit][tile] counts are scanned in chunks of
+# FLUSH_SCAN_CHUNK (FLUSH_SCAN_CHUNK // 256 tiles fill one chunk).
+FLUSH_TILE = 4096
+FLUSH_BLOCK_CAP = 8192
+FLUSH_SCAN_CHUNK = 16384
+
+
+def flush_batch(ops, drop_tombstones: bool = False, filter: BloomFilter | None = None,
+                device: int = 0, out=None, stream=None):
+    """Batched PUT (bloomhip_flush_batch): ops = entry_t records in arrival
+    order (an int32 [n, 2] numpy array or device tensor; a delete is a record
+    whose value is VAL_NONE).  Returns the run a flush of them writes: one entry
+    per key, keys ascending, the last op's value (a [n_out, 2] int32 array, or
+    the first n_out rows of `out` when given); builds `filter` (and its run
+    metadata) from the run's keys when given."""
+    dt = str(ops.dtype)
+    if dt not in ("int32", "torch.int32") or len(ops.shape) != 2 or ops.shape[1] != 2:
+        raise ValueError(f"ops must be an int32 [n, 2] entry_t array (got {dt} {tuple(ops.shape)})")
+    ptr, on_dev, keep = _ptr_of(ops)
+    n = _nbytes(keep) // 8
+    if out is None:
+        out = np.empty((max(n, 1), 2), dtype=np.int32)
+    optr, out_dev, okeep = _out_ptr(out, n * 8, 4, "out")
+    n_out = ctypes.c_size_t()
+    _check(_lib().bloomhip_flush_batch(ptr if n else None, n, on_dev, 1 if drop_tombstones else 0,
+                                       optr, ctypes.byref(n_out), out_dev,
+                                       filter.handle if filter is not None else None,
+                                       filter.device if filter is not None else device,
+                                       _stream_ptr(stream)), "bloomhip_flush_batch")
     return out[:n_out.value]
 
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/bloomhip.h"
+#include "bloom_flush.h"
 #include "bloom_kernels.h"
 #include "bloom_merge.h"
 #include "bloom_range.h"
@@ -239,6 +240,8 @@ struct Workspace {
     // tables, host entries staged, the large queries' slices, host output staged
     void *rbuf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     size_t rbuf_bytes[5] = {0, 0, 0, 0, 0};
+    uint32_t *fcount = nullptr;  // batched PUT: digit histograms, tile counts, chunk totals
+    size_t fcount_bytes = 0;
 };
 enum RangeBuf { RBUF_TABLES = 0, RBUF_LARGE = 1, RBUF_ENTRIES = 2, RBUF_SLICES = 3, RBUF_OUT = 4 };
 
@@ -278,7 +281,7 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     for (void **p : {(void **)&w->pos, (void **)&w->runs, (void **)&w->res, (void **)&w->slots,
                      &w->mbuf[0], &w->mbuf[1], (void **)&w->msplit, (void **)&w->mcount,
                      (void **)&w->mkeys, &w->kway, &w->rbuf[0], &w->rbuf[1], &w->rbuf[2], &w->rbuf[3],
-                     &w->rbuf[4]}) {
+                     &w->rbuf[4], (void **)&w->fcount}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -286,7 +289,7 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     w->h_kept = w->d_kept = nullptr;
     w->pos_bytes = w->runs_bytes = w->res_bytes = w->slots_bytes = 0;
     w->mbuf_bytes[0] = w->mbuf_bytes[1] = w->msplit_bytes = w->mcount_bytes = w->mkeys_bytes = 0;
-    w->kway_bytes = 0;
+    w->kway_bytes = w->fcount_bytes = 0;
     for (size_t &b : w->rbuf_bytes) b = 0;
 }
 
@@ -1604,6 +1607,132 @@ int bloomhip_compact(const void *const *runs, const size_t *nentries, int nruns,
         void *dst = nullptr;
         rc = compact_device(w.get(), std::move(list), total, drop_tombstones,
                             out_on_device ? out_entries : nullptr, !runs_on_device, f, s, &kept, &dst);
+        if (rc) return rc;
+        if (!out_on_device && kept)
+            HIP_TRY(hipMemcpyAsync(out_entries, dst, kept * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *n_out = (size_t)kept;
+    return BLOOMHIP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// BLOOMHIP_FLUSH_PATH = auto | tiled, read per call: tiled sends a batch that
+// one workgroup could sort down the multi-launch path (for tests).
+bool flush_path_tiled() {
+    const char *e = getenv("BLOOMHIP_FLUSH_PATH");
+    return e && !strcmp(e, "tiled");
+}
+
+// The device part of bloomhip_flush_batch: n ops at src (device; mbuf[0] when
+// they were staged), 0 < n < 2^32 - 1, compact_reserve and fcount done, w
+// locked.  The run goes to `out` when given (a device buffer), else to a
+// workspace buffer; *result is where it is and *kept_out its length.
+int flush_device(Workspace *w, const void *src, uint64_t n, int drop_tombstones, void *out,
+                 bloomhip_filter *f, hipStream_t s, uint64_t *kept_out, void **result) {
+    uint32_t cnt = 0;
+    void *dst = nullptr;
+    if (n <= kFlushBlockCap && !flush_path_tiled()) {
+        // one workgroup, one launch: every digit pass and the dedup in LDS
+        dst = out ? out : w->mbuf[1];
+        hipError_t e = launch_flush_block(src, n, drop_tombstones, dst, f ? w->mkeys : nullptr,
+                                          w->fcount, s);
+        if (e != hipSuccess) return fail_hip(e, "flush block launch");
+        HIP_TRY(hipMemcpyAsync(&cnt, w->fcount, 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    } else {
+        // the digit histograms say which passes move anything
+        uint32_t hist[kFlushPasses * kFlushBins];
+        hipError_t e = launch_flush_hist(src, n, w->fcount, s);
+        if (e != hipSuccess) return fail_hip(e, "flush histogram launch");
+        HIP_TRY(hipMemcpyAsync(hist, w->fcount, sizeof hist, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        uint32_t passes = flush_pass_mask(hist, n);
+        if (!passes) passes = 1;  // one key: pass 0 still turns the ops newest first
+        // The first pass reads the ops back to front; the passes ping-pong
+        // between the two buffers, never writing the one they read, and the
+        // sorted ops always end in a workspace buffer, which the dedup reads.
+        const void *cur = src;
+        bool first = true;
+        for (int p = 0; p < kFlushPasses; p++) {
+            if (!(passes >> p & 1)) continue;
+            void *to = w->mbuf[cur == w->mbuf[0] ? 1 : 0];
+            e = launch_flush_pass(cur, n, first, p, to, w->fcount, s);
+            if (e != hipSuccess) return fail_hip(e, "flush pass launch");
+            cur = to;
+            first = false;
+        }
+        // equal keys are newest first: the compaction's dedup keeps the first
+        dst = out ? out : w->mbuf[cur == w->mbuf[0] ? 1 : 0];
+        e = launch_dedup(cur, n, drop_tombstones, dst, w->mcount, s, f ? w->mkeys : nullptr);
+        if (e != hipSuccess) return fail_hip(e, "dedup launch");
+        HIP_TRY(hipMemcpyAsync(&cnt, w->mcount + compact_count_words(n) - 1, 4,
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    if (cnt > n) return fail_hip(hipErrorUnknown, "flush kept count out of range");
+    if (f) {
+        int rc = cnt ? set_batch_run_locked(f, w->mkeys, (size_t)cnt, 4, 1, s, true)
+                     : set_batch_run_locked(f, dst, 0, 8, 1, s, true);
+        if (rc) return rc;
+    }
+    *kept_out = cnt;
+    *result = dst;
+    return BLOOMHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bloomhip_flush_batch(const void *ops, size_t n, int ops_on_device, int drop_tombstones,
+                         void *out_entries, size_t *n_out, int out_on_device, bloomhip_filter *f,
+                         int device, void *stream) {
+    g_last_error.clear();
+    if (!n_out) return BLOOMHIP_EINVAL;
+    if (n && (!ops || !out_entries)) return BLOOMHIP_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(ops) & (ops_on_device ? 7 : 3)) ||
+        (reinterpret_cast<uintptr_t>(out_entries) & (out_on_device ? 7 : 3)))
+        return BLOOMHIP_EINVAL;
+    if (f && f->device != device) return BLOOMHIP_EINVAL;
+    if (n >= 0xFFFFFFFFull) return BLOOMHIP_ERANGE;  // 32-bit offsets, as bloomhip_compact
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BLOOMHIP_ENODEV;
+    if (device < 0 || device >= ndev) return BLOOMHIP_EINVAL;
+    DeviceGuard g(device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    uint64_t kept = 0;
+    {
+        // filter first, then workspace: the global lock order
+        std::unique_lock<std::mutex> flk;
+        if (f) flk = std::unique_lock<std::mutex>(f->mu);
+        if (n == 0) {
+            if (f) {  // the run of no keys: an empty filter, empty metadata
+                f->pending_clear = true;
+                f->known_zero = true;
+                int rc = set_batch_run_locked(f, nullptr, 0, 8, 1, s, true);
+                if (rc) return rc;
+                HIP_TRY(hipStreamSynchronize(s));
+            }
+            *n_out = 0;
+            return BLOOMHIP_OK;
+        }
+        const LockedWorkspace w(device, s);
+        int rc = compact_reserve(w.get(), n, 1, f != nullptr, s);
+        if (rc) return rc;
+        HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->fcount), &w->fcount_bytes,
+                             flush_workspace_words(n) * 4, s));
+        const void *src = ops;
+        if (!ops_on_device) {
+            HIP_TRY(hipMemcpyAsync(w->mbuf[0], ops, n * 8, hipMemcpyHostToDevice, s));
+            src = w->mbuf[0];
+        }
+        void *dst = nullptr;
+        rc = flush_device(w.get(), src, n, drop_tombstones, out_on_device ? out_entries : nullptr,
+                          f, s, &kept, &dst);
         if (rc) return rc;
         if (!out_on_device && kept)
             HIP_TRY(hipMemcpyAsync(out_entries, dst, kept * 8, hipMemcpyDeviceToHost, s));

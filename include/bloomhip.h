@@ -304,6 +304,49 @@ int bloomhip_range_batch(const bloomhip_filter *const *runs, const void *const *
                          uint64_t *offsets, void *out_entries, size_t out_capacity,
                          size_t *total_out, int out_on_device, int device, void *stream);
 
+/* --- batched PUT: a batch of puts and deletes sorted into a run -------------
+ * The write side up to a flush.  LSMTree::put (src/lsm_tree.cpp:104-139)
+ * inserts into Buffer, a std::set<entry_t> ordered by key, where a second put
+ * of a key replaces the first (src/buffer.cpp:37-58); del is a put of
+ * VAL_TOMBSTONE (src/lsm_tree.cpp:292-294) and load a put per record of a
+ * binary file (:296-309).  A flush walks the set in key order into a new
+ * level-0 run (:124-131), Run::put setting filter bits and fences on the way.
+ * ops: n entry_t {int32 key; int32 val;} records in arrival order, a delete
+ * being a record whose val is INT32_MIN; host memory (4-byte aligned) unless
+ * ops_on_device (8-byte aligned).  ops is not modified.
+ * The answer is what iterating Buffer::entries gives after Buffer::put of
+ * every op in order, with a buffer large enough never to refuse: one entry per
+ * distinct key, keys strictly ascending as signed int32, each carrying the
+ * value of the LAST op on its key.  With drop_tombstones (level 0 is the
+ * tree's last level, as in bloomhip_compact) entries whose surviving value is
+ * INT32_MIN are left out: a delete followed by a put of the key survives, a
+ * put followed by a delete does not.
+ * out_entries (capacity n entries; host, or on `device` when out_on_device;
+ * aligned as ops; must not overlap ops) receives the run and *n_out its
+ * length.  When f is not NULL the new run's filter and metadata are built
+ * from the output keys in the same call (bloomhip_set_batch_run on the device
+ * copy), exactly as bloomhip_compact does it.  Synchronous (the length is
+ * returned).
+ * n == 0: *n_out = 0; f, if given, is cleared and receives the metadata of a
+ * run of no keys.
+ * Checked before any HIP call, in this order: BLOOMHIP_EINVAL for n_out ==
+ * NULL, for n > 0 with ops or out_entries NULL, for a misaligned ops or
+ * out_entries, for f on another device than `device`; BLOOMHIP_ERANGE for
+ * n >= 2^32 - 1 (32-bit offsets, bloomhip_compact's limit).  Then
+ * BLOOMHIP_ENODEV without a GPU and BLOOMHIP_EINVAL for a bad device.
+ * BLOOMHIP_FLUSH_PATH = auto | tiled (environment, read per call): a batch
+ * that fits one workgroup's LDS is sorted and de-duplicated in one launch;
+ * tiled sends it down the multi-launch radix sort instead (for tests).
+ * Deviation from the reference: it decides the flush boundaries itself.
+ * Buffer::put refuses once the buffer holds max_size distinct keys, even for
+ * a key already in it (src/buffer.cpp:42), and the tree flushes then.  Here
+ * the caller chooses the batch.  A larger batch gives the same GET and RANGE
+ * answers (newest-wins is associative) but other run boundaries; finding the
+ * reference's own cut points in an op stream is left to the caller. */
+int bloomhip_flush_batch(const void *ops, size_t n, int ops_on_device, int drop_tombstones,
+                         void *out_entries, size_t *n_out, int out_on_device,
+                         bloomhip_filter *f, int device, void *stream);
+
 /* Scalar compatibility entry points (one key; synchronous), for
  * BloomFilter::set (src/bloom_filter.cpp:49-53) and is_set (:55-59) called
  * once per key.  Low-latency path: the key travels as a kernel argument (no
