@@ -53,6 +53,8 @@ namespace {
 //   kPrioYoung:   by waves TB/128 .. TB/64 - 1 of each workgroup for the whole
 //                 kernel, set once, no flips.
 // pass1_prio chooses; only kPrioHash measured faster anywhere.
+// a stamped pipelined build's u64 stamps per workgroup (k_part_bin's STAMP)
+constexpr int kEdge1Start = 0, kEdge1End = 1, kEdge1Tile0 = 2, kEdgeStamps1 = 32;
 constexpr int kPrioSort = 0, kPrioScatter = 1, kPrioHash = 2, kPrioYoung = 3;
 constexpr int pass1_prio_of(int mode, int level) { return level | mode << 2; }
 
@@ -123,6 +125,9 @@ constexpr uint32_t kBinShift = 19;  // 8192 segments << 19 < 2^32
 // << 16, b = 0..nbins-1): COLS = true: straight into the segment-major table
 // runs[b * ntiles + tile]; COLS = false: into the tile-major
 // runs[tile * nbins + b], for k_runs_transpose (large tables).
+// How k_part_bin stores its sorted tiles (ST): plain, non-temporal
+// (pass1_may_nt) or write-through (pass1_wt).
+constexpr int kStorePlain = 0, kStoreNT = 1, kStoreWT = 2;
 constexpr int kModFast = 0, kModWide = 1, kModP2 = 2, kModLadder = 3, kModLadder0 = 4;
 // plan_build's one-member ladder with the block relabelled to (x >> 24) % d
 // (bloom_math.h mod_p2_hi24; ladder0_relabel): C2 and C5
@@ -206,7 +211,7 @@ __device__ __forceinline__ void bin_entry(uint64_t raw, const ModParams &mp, con
 // scatter interleaved with the hashing (it needs the scan's offsets to stay
 // inside the image, so it cannot be priced before the scan).
 template <int LAYOUT, bool SLOTS, bool COLS, int TB, int MK, int MAXB = 0, int MINW = 4,
-          int ABL = 0, bool NT = false, bool DEFER = false, int PRIO = 0, int PIPE = 0>
+          int ABL = 0, int ST = kStorePlain, bool DEFER = false, int PRIO = 0, int PIPE = 0, bool STAMP = false>
 __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
                                                        uint64_t *__restrict__ pos_out,
                                                        uint32_t *__restrict__ runs, SegMap sm,
@@ -262,12 +267,17 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
         }
         const uint4 v = pack_entries6(e);
         if constexpr (ABL == 0) {
-            // NT: sorted tiles beyond the Infinity Cache (C5: 512 MiB) are
-            // stored non-temporal, so they do not evict what pass 2 can use
-            // there (C5 build 0.419 -> 0.406 ms; below it, C2's 128 MiB,
+            // kStoreNT: sorted tiles beyond the Infinity Cache (C5: 512 MiB)
+            // are stored non-temporal, so they do not evict what pass 2 can
+            // use there (C5 build 0.419 -> 0.406 ms; below it, C2's 128 MiB,
             // pass 2 reads them from the cache: 35 us, 48 from HBM; a
-            // runtime choice in the kernel spilled 3-4 VGPRs)
-            if constexpr (NT) nt_store16(dst, v);
+            // runtime choice in the kernel spilled 3-4 VGPRs).
+            // kStoreWT: written through (pass1_wt), so the kernel ends
+            // with no dirty tile lines in the L2s for the boundary to flush;
+            // pass 2 still reads them from the Infinity Cache.
+            if constexpr (ST == kStoreNT) nt_store16(dst, v);
+            else if constexpr (ST == kStoreWT)
+                wt_store16(pos_out + tile * (size_t)kTileKeys, 16u * (uint32_t)(r * TB + tid), v);
             else *dst = v;
         } else {
             // keep the packing: a store only when an impossible value shows
@@ -475,6 +485,28 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
     const size_t nfull = ks.n / kTileKeys;
     size_t tile = part_tile(0, ntiles);
     if (tile >= ntiles) return;
+    // STAMP (micro-benchmarks only, tools/ubench.py edges): the pipelined
+    // build's workgroup x writes wall_clock64() into slots[x * kEdgeStamps1 ..]
+    // as u64 (a build has no slot plane), thread 0 alone, with an ordinary
+    // store: its start, its end (every store complete), then one stamp after
+    // each iteration of the tile loop and after the epilogue.
+    static_assert(!STAMP || (PIPE != 0 && !SLOTS), "stamps: the pipelined build");
+    int nstamp = kEdge1Tile0;
+    auto stamp = [&](int k) {
+        if constexpr (STAMP) {
+            if (tid == 0 && k < kEdgeStamps1)
+                reinterpret_cast<uint64_t *>(slots)[(size_t)blockIdx.x * kEdgeStamps1 + k] = wall_clock64();
+        }
+    };
+    auto stamp_end = [&]() {
+        if constexpr (STAMP) {
+            stamp(nstamp++);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            stamp(kEdge1End);
+        }
+    };
+    stamp(kEdge1Start);
     if constexpr (PRIO != 0 && kPrioMode == kPrioYoung) {
         // the workgroup's later-dispatched half; the wave index from an SGPR,
         // so the branch is scalar (s_setprio ignores EXEC)
@@ -619,26 +651,32 @@ __global__ void __launch_bounds__(TB, MINW) k_part_bin(KeySpan ks, ModParams mp,
         lds_barrier_prio<kPrioAtHist>();
         if (tile >= nfull) {  // the block's only tile is the short one
             pipe_tile(BoolC<false>{}, BoolC<false>{}, tile, ntiles, tile, 0u);
+            stamp(nstamp++);
             pipe_last(BoolC<false>{}, tile);
+            stamp_end();
             return;
         }
         size_t prev = tile, next = part_tile(1, ntiles);
         pipe_tile(BoolC<true>{}, BoolC<false>{}, tile, next, tile, 0u);
+        stamp(nstamp++);
         tile = next;
         uint32_t hoff = kHist;
         for (size_t round = 2; tile < nfull; round++) {
             next = part_tile(round, ntiles);
             pipe_tile(BoolC<true>{}, BoolC<true>{}, tile, next, prev, hoff);
+            stamp(nstamp++);
             prev = tile;
             tile = next;
             hoff = kHist - hoff;
         }
         if (tile < ntiles) {
             pipe_tile(BoolC<false>{}, BoolC<true>{}, tile, ntiles, prev, hoff);
+            stamp(nstamp++);
             pipe_last(BoolC<false>{}, tile);
         } else {
             pipe_last(BoolC<true>{}, prev);
         }
+        stamp_end();
     } else if constexpr (!DEFER) {
         for (size_t round = 0; tile < nfull; round++) {
             const size_t next = part_tile(round + 1, ntiles);
@@ -1030,7 +1068,8 @@ struct Pass1Kernel {
     int mk;          // MK: the reduction kind, kMod*
     int maxb;        // MAXB: histogram capacity
     int wgs_per_cu;  // resident workgroups per CU: MINW = pass1_min_waves(threads, wgs_per_cu)
-    bool nt;         // NT: the sorted tiles stored non-temporal
+    bool nt;         // ST = kStoreNT: the sorted tiles stored non-temporal
+    bool wt;         // ST = kStoreWT: the sorted tiles stored write-through
     bool defer;      // DEFER: a tile's write-out inside the next tile's hash phase
     unsigned grid;   // persistent workgroups
     int prio;        // PRIO: the phases' issue priority (pass1_prio_of), 0 = none
@@ -1129,11 +1168,21 @@ constexpr int pass1_pipe(int threads, bool slots, int wgs_per_cu, int mk) {
 }
 
 // builds whose sorted tiles exceed the Infinity Cache (C5): stored
-// non-temporal (k_part_bin's NT); compiled for the 1024-thread builds at
+// non-temporal (k_part_bin's kStoreNT); compiled for the 1024-thread builds at
 // MAXB 1023 alone
 constexpr bool pass1_may_nt(int threads, bool slots, int maxb) {
     return !slots && threads >= 1024 && maxb == 1023;
 }
+
+// builds from packed keys in the family of the pipelined loop (C2), while the
+// sorted tiles fit the Infinity Cache (choose_pass1_kernel checks the size):
+// stored write-through (k_part_bin's kStoreWT).  With plain stores pass 1
+// ends with the L2s full of dirty tile lines, which are flushed at the kernel
+// boundary while nothing runs.  Measured in this family alone, so entry_t
+// keys (at the edge of their spread written through), every other family
+// and batches beyond the Infinity Cache keep their stores
+// (profiles/build_edges/README.md).
+constexpr bool pass1_wt(int pipe, int layout) { return pipe != 0 && layout == KEYS_PACKED; }
 
 // Whether pass 1 may take the p2 reduction (kModP2) for this geometry: the
 // entry must be the hash's low kEntryBits bits (t >= 21) and p >> shift must
@@ -1201,6 +1250,8 @@ inline bool choose_pass1_kernel(const KeySpan &ks, const ModParams &mp, const Pa
            ws.ntiles * (uint64_t)(p.threads * kPartKPT) * 8 > kInfinityCacheBytes;
     p.prio = p.super ? 0 : pass1_prio(p.threads, slots, p.wgs_per_cu);
     p.pipe = p.super ? 0 : pass1_pipe(p.threads, slots, p.wgs_per_cu, p.mk);
+    p.wt = !p.nt && pass1_wt(p.pipe, p.layout) &&
+           ws.ntiles * (uint64_t)(p.threads * kPartKPT) * 8 <= kInfinityCacheBytes;
     p.cols = runs_as_columns(ws);
     p.grid = pass1_grid(ws.ntiles, ncu, p.wgs_per_cu);
     *out = p;
@@ -1230,19 +1281,31 @@ bool launch_pass1_tile(const Pass1Kernel &p, const KeySpan &ks, const ModParams 
                     constexpr bool kMayNT = pass1_may_nt(TB, SLOTS, MAXB);
                     constexpr int kPrio = pass1_prio(TB, SLOTS, kWgs);
                     constexpr int kPipe = pass1_pipe(TB, SLOTS, kWgs, MK);
-                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT) || p.prio != kPrio || p.pipe != kPipe) return false;
-                    auto go = [&](auto cols_c, auto nt_c) {
-                        k_part_bin<L, SLOTS, decltype(cols_c)::value, TB, MK, MAXB, kMinW, 0,
-                                   decltype(nt_c)::value, kDefer, kPrio, kPipe>
+                    constexpr bool kMayWT = pass1_wt(kPipe, L);
+                    if (p.wgs_per_cu != kWgs || (p.nt && !kMayNT) || p.prio != kPrio || p.pipe != kPipe ||
+                        (p.wt && !kMayWT) || (p.nt && p.wt))
+                        return false;
+                    auto go = [&](auto cols_c, auto st_c) {
+                        k_part_bin<L, SLOTS, decltype(cols_c)::value, TB, MK, MAXB, kMinW, 0, decltype(st_c)::value,
+                                   kDefer, kPrio, kPipe>
                             <<<p.grid, TB, 0, stream>>>(ks, mp, ws.pos, runs, sm, ws.ntiles, slots);
                     };
+                    using StNT = std::integral_constant<int, kStoreNT>;
+                    using StWT = std::integral_constant<int, kStoreWT>;
+                    using StPlain = std::integral_constant<int, kStorePlain>;
                     if constexpr (kMayNT) {
                         if (p.nt) {
-                            p.cols ? go(BoolC<true>{}, BoolC<true>{}) : go(BoolC<false>{}, BoolC<true>{});
+                            p.cols ? go(BoolC<true>{}, StNT{}) : go(BoolC<false>{}, StNT{});
                             return true;
                         }
                     }
-                    p.cols ? go(BoolC<true>{}, BoolC<false>{}) : go(BoolC<false>{}, BoolC<false>{});
+                    if constexpr (kMayWT) {
+                        if (p.wt) {
+                            p.cols ? go(BoolC<true>{}, StWT{}) : go(BoolC<false>{}, StWT{});
+                            return true;
+                        }
+                    }
+                    p.cols ? go(BoolC<true>{}, StPlain{}) : go(BoolC<false>{}, StPlain{});
                     return true;
                 } else {
                     return false;

@@ -21,6 +21,11 @@ constexpr int kApplyBlock = 1024;
 // pass 2's prologue: loads per thread in flight while an LDS image is staged
 constexpr int kStageBatch = 4;
 constexpr int kApplyDepth = 2;  // lane-group loads per wave per batch
+// a stamped build's u64 stamps per workgroup (k_part_apply's STAMP): its start,
+// the image staged (past the barrier), the first entry vector arrived, the
+// walk done (past its barrier), the write-out's stores complete
+constexpr int kEdge2Start = 0, kEdge2Staged = 1, kEdge2FirstVec = 2, kEdge2Walked = 3, kEdge2End = 4;
+constexpr int kEdgeStamps2 = 5;
 
 // MODE kApplyBuild: OR every entry into the zeroed LDS image, write the
 // segment.  kApplyProbe: the LDS image is the filter's segment; each entry's
@@ -164,12 +169,34 @@ __device__ __forceinline__ uint32_t stack_bits(const uint32_t *seg, uint32_t o,
 }
 
 template <int MODE, int G, int TILE_KEYS, int BLOCK = kApplyBlock, int DEPTH = kApplyDepth,
-          int CHAINS = 0, int VECS = 1, bool REDIR = false, int NF = 0, int LK = 0>
+          int CHAINS = 0, int VECS = 1, bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false>
 __global__ void __launch_bounds__(BLOCK) k_part_apply(
     const uint64_t *__restrict__ pos, const uint32_t *__restrict__ run_starts, int ntiles,
     int nbins, uint32_t seg_bits, uint64_t m, uint32_t *__restrict__ words, uint64_t nw32,
     int merge_existing, uint8_t *__restrict__ res, StackTable st) {
     constexpr bool PROBE = MODE != kApplyBuild && MODE != kApplyBuildL;
+    // A fresh filter's bitmap is stored write-through by the builds that were
+    // measured with it: the group walk at one vector per lane without the
+    // redirect, on 4096- and 8192-key tiles (choose_apply_walk: C2 with pass
+    // 1's write-through tiles 0.0789-0.0797 -> 0.0776-0.0788 ms, the f = 10
+    // build and the general remainder level or slightly faster).  Every other build
+    // keeps the non-temporal store: C5 (two vectors per lane, entries from
+    // HBM) measured 0.3854 -> 0.3896 written through, and the short-run and
+    // super-tile builds (C4) were not measured (profiles/build_edges/README.md).
+    constexpr bool kFreshWT =
+        !PROBE && CHAINS == 1 && VECS == 1 && !REDIR && TILE_KEYS != (int)kSuperTileKeys;
+    // STAMP (micro-benchmarks only, tools/ubench.py edges): a build's
+    // workgroup b writes wall_clock64() at its kEdge2* stages into
+    // res[b * kEdgeStamps2 ..] as u64 (a build has no result bytes), thread
+    // 0 alone, with an ordinary store.
+    static_assert(!STAMP || (!PROBE && CHAINS == 1 && VECS == 1), "stamps: the build's group walk");
+    auto stamp = [&](int k) {
+        if constexpr (STAMP) {
+            if (threadIdx.x == 0)
+                reinterpret_cast<uint64_t *>(res)[(size_t)blockIdx.x * kEdgeStamps2 + k] = wall_clock64();
+        }
+    };
+    stamp(kEdge2Start);
     static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "G lanes per tile");
     constexpr int kTilePos = 3 * TILE_KEYS;
     constexpr int kTPI = 64 / G;                 // tiles per load instruction
@@ -383,6 +410,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             reinterpret_cast<uint4 *>(seg)[i] = make_uint4(0, 0, 0, 0);
     }
     __syncthreads();
+    stamp(kEdge2Staged);
 
     const int lane = tix & 63;
     const int wave = tix >> 6;
@@ -573,6 +601,10 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
         uint32_t r = bnd(t), rn = bnd(t + Q);
         uint32_t vb = (r & 0xFFFFu) / 6u;  // the group's step base (vector index)
         uint4 v = load(min(t, ntiles - 1), vload(vb + sub, vb, r >> 16));
+        if constexpr (STAMP) {  // the first vector has arrived
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            stamp(kEdge2FirstVec);
+        }
         while (__ballot(t < ntiles) != 0) {
             // state after this step: advance within the run or to the next
             // tile.  On a tile change the new lookahead bounds are loaded
@@ -733,6 +765,15 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
         return;
     }
     __syncthreads();
+    stamp(kEdge2Walked);
+    // (stamped: the write-out's stores have left the wave)
+    auto stamp_end = [&]() {
+        if constexpr (STAMP) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            stamp(kEdge2End);
+        }
+    };
 
     if constexpr (MODE == kApplyBuildL) {
         // block a of the image (2^s bits) is the bitmap's bits a << t | b << s;
@@ -759,8 +800,17 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
                 *dq = v;
             }
         } else {
-            for (uint32_t q = tix; q < st.lad.d * vpb; q += BLOCK) nt_store16(block(q), seg4[q]);
+            // (the segments' note below; block(q) as a byte offset from this
+            // bin's first block: the ladder is a build of m < 2^32 bits)
+            if constexpr (kFreshWT) {
+                uint4 *b0 = w4 + ((size_t)b << (ls - 7));
+                for (uint32_t q = tix; q < st.lad.d * vpb; q += BLOCK)
+                    wt_store16(b0, (uint32_t)((const char *)block(q) - (const char *)b0), seg4[q]);
+            } else {
+                for (uint32_t q = tix; q < st.lad.d * vpb; q += BLOCK) nt_store16(block(q), seg4[q]);
+            }
         }
+        stamp_end();
         return;
     }
 
@@ -782,7 +832,14 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             // Gkeys/s in the bench A/B); a merge stores plainly what it has
             // just read (re-reading a non-temporal bitmap in repeated merges
             // cost C2 0.0909 -> 0.0917 ms)
-            for (int q = tix; q < (int)seg_words / 4; q += BLOCK) nt_store16(dst4 + q, seg4[q]);
+            // kFreshWT: written through instead, so that pass 2 ends with
+            // none of the bitmap dirty in the L2s
+            if constexpr (kFreshWT) {
+                for (int q = tix; q < (int)seg_words / 4; q += BLOCK)
+                    wt_store16(dst4, 16u * (uint32_t)q, seg4[q]);
+            } else {
+                for (int q = tix; q < (int)seg_words / 4; q += BLOCK) nt_store16(dst4 + q, seg4[q]);
+            }
         }
     } else {
         for (int i = tix; i < nseg; i += BLOCK) {
@@ -791,6 +848,7 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
             dst[i] = v;
         }
     }
+    stamp_end();
     }
     segment_done:
         if (!seg_stride) return;
@@ -853,7 +911,7 @@ inline void stack_stride(size_t nbins, uint32_t seg_words, size_t lds, StackTabl
 // Launches pass 2 (build or probe) with S/8 bytes of dynamic LDS (> 64 KiB
 // must be opted into per kernel).
 template <int MODE, int G, int TK, int DEPTH = kApplyDepth, int CHAINS = 0, int VECS = 1,
-          bool REDIR = false, int NF = 0, int LK = 0>
+          bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false>
 hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *words,
                           uint64_t nw32, int merge, uint8_t *res, const StackTable &st,
                           hipStream_t stream) {
@@ -864,7 +922,7 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     // instantiation from the code object, and the launch refused otherwise.
     static const bool lds_ok = [] {
         const void *fn = reinterpret_cast<const void *>(
-            &k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK>);
+            &k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP>);
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(kStackMaxBits / 8));
         hipFuncAttributes fa{};
@@ -879,7 +937,7 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     sk.keep_mask = 0;
     if (MODE == kApplyStack && NF < 8 && G == 4) stack_stride(ws.nbins, ws.seg_bits / 32, lds, sk);
     const unsigned grid = sk.seg_stride ? (unsigned)sk.seg_stride : (unsigned)ws.nbins;
-    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK>
+    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP>
         <<<grid, kApplyBlock, lds, stream>>>(ws.pos, ws.run_starts, (int)ws.ntiles, (int)ws.nbins,
                                              ws.seg_bits, m, words, nw32, merge, res, sk);
     return hipGetLastError();

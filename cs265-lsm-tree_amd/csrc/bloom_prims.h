@@ -1,7 +1,8 @@
 // bloom_prims.h — device primitives shared by the partition kernels (key
 // loads, the wave scan, one-instruction shift-ors, the LDS barriers and
 // absolute-address LDS reads, the sorted tiles' packing, the XCD map, the
-// non-temporal store) and the two compile-time helpers of their launchers.
+// non-temporal and the write-through store) and the two compile-time helpers
+// of their launchers.
 //
 // Bit-exact restatement of jackdent/cs265-lsm-tree src/bloom_filter.cpp:49-59
 // over batches of int32 keys; the bitmap is dynamic_bitset<unsigned long>'s
@@ -124,6 +125,22 @@ __device__ __forceinline__ void nt_store16(uint4 *p, const uint4 &v) {
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     const v4u x = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(x, reinterpret_cast<v4u *>(p));
+}
+
+// A 16-B write-through (sc1) store at byte offset off of a wave-uniform
+// base: the line goes to memory as it is stored and leaves the writer's L2, so
+// nothing of it is left to flush at the kernel's end.  A buffer store (the
+// base in SGPRs, counted in vmcnt like any store); off < 4 GiB.
+// The whole offset travels in the VGPR operand: with part of it in the SGPR
+// offset operand pass 1 wrote wrong tiles (cause not found;
+// profiles/build_edges/README.md section 4), so soffset stays 0 with this
+// descriptor.
+__device__ __forceinline__ void wt_store16(void *base, uint32_t off, const uint4 &v) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const v4u x = {v.x, v.y, v.z, v.w};
+    // raw buffer: stride 0, no bound (num_records ~0), 32-bit data format
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(base, 0, -1, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(x, rsrc, (int)off, 0, /*aux: sc1*/ 16);
 }
 
 // f(integral_constant<V>) for the V of Vs that equals v; false when none

@@ -502,6 +502,101 @@ extern "C" int ubench_part_walk(int chains, int vecs, int redir, const void *key
     return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -22 : -5;
 }
 
+// The product's build on a forced pass-1 grid: the kernel choose_pass1_kernel
+// gives (store policy included), launched on min(grid, tiles) persistent
+// workgroups, then the product's pass 2.  A small grid runs the tile loop of
+// the persistent kernels (peeled first tile, steady state, partial last round,
+// ragged last tile, epilogue) at batches of a few tiles
+// (tests/test_gpu_build_edges.py).  entry_keys: the keys are entry_t records
+// (stride 8).  ubench_part_walk's signature; buffers as for ubench_part.
+extern "C" int ubench_part_grid(int grid, int entry_keys, int merge, const void *keys, size_t n,
+                                uint64_t m, uint64_t *pos, uint32_t *runs, uint32_t *words,
+                                void *stream, size_t pos_cap, size_t runs_cap) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const KeySpan ks{reinterpret_cast<const char *>(keys), n, entry_keys ? (size_t)8 : (size_t)4,
+                     entry_keys ? KEYS_ENTRY : KEYS_PACKED};
+    const ModParams mp = make_mod_params(m);
+    PartitionWorkspace ws{};
+    int mode = 0;
+    if (n == 0 || grid < 1) return -22;
+    if (!build_plan(n, m, device_cu_count(), &ws, &mode)) return -34;
+    if (ws.ntiles * ws.tile_keys > pos_cap || 2 * ws.ntiles * (ws.nbins + 1) > runs_cap) return -28;
+    ws.pos = pos;
+    ws.run_rows = runs;
+    ws.run_starts = runs + ws.ntiles * (ws.nbins + 1);
+    Pass1Kernel p{};
+    SegMap sm{};
+    if (!choose_pass1_kernel(ks, mp, ws, false, device_cu_count(), &p, &sm)) return -22;
+    p.grid = (unsigned)std::min<size_t>((size_t)grid, ws.ntiles);
+    Pass1Launch *unit = p.super ? launch_bin_super : p.threads >= 1024 ? launch_bin_build1024 : launch_bin_build512;
+    if (!unit(p, ks, mp, ws, sm, nullptr, s)) return -22;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && !p.cols) e = launch_runs_transpose(ws, s);
+    if (e == hipSuccess) e = launch_part_apply(mp, words, ws, merge, s);
+    if (e != hipSuccess) fprintf(stderr, "ubench_part_grid: %s\n", hipGetErrorString(e));
+    // the pass-1 kernel's store policy and loop, for the caller to check what ran
+    return e == hipSuccess ? (p.wt ? 2 : p.nt ? 1 : 0) | (p.pipe ? 4 : 0) : -5;
+}
+
+// The stamps' layout: u64 stamps per workgroup of pass 1 and of pass 2.
+extern "C" void ubench_edge_layout(int *out2) {
+    out2[0] = kEdgeStamps1;
+    out2[1] = kEdgeStamps2;
+}
+
+// The C2 build's two kernels stamped (k_part_bin's and k_part_apply's STAMP),
+// one after the other in one stream (tools/ubench.py edges): pass 1's
+// workgroup x stamps at stamps[x * kEdgeStamps1 ..], pass 2's workgroup b at
+// stamps[grid1 * kEdgeStamps1 + b * kEdgeStamps2 ..].  out4: pass 1's grid,
+// pass 2's, pass 1's rounds, the stamps' clock in kHz.  Buffers as for
+// ubench_part; only the geometry of UB_PIPE (plan_build's relabelled
+// one-member ladder on 4096-key tiles).
+extern "C" int ubench_edges(const void *keys, size_t n, uint64_t m, uint64_t *pos, uint32_t *runs,
+                            uint32_t *words, void *stream, size_t pos_cap, size_t runs_cap,
+                            uint64_t *stamps, size_t stamps_cap, int *out4) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const KeySpan ks{reinterpret_cast<const char *>(keys), n, 4, KEYS_PACKED};
+    const ModParams mp = make_mod_params(m);
+    PartitionWorkspace ws{};
+    if (n == 0 || !plan_build(m, device_cu_count(), &ws)) return -34;
+    if (!ws.tile_keys) ws.tile_keys = choose_tile_keys(ws.nbins);
+    ws.ntiles = (n + ws.tile_keys - 1) / ws.tile_keys;
+    if (ws.ntiles * ws.tile_keys > pos_cap || 2 * ws.ntiles * (ws.nbins + 1) > runs_cap) return -28;
+    ws.pos = pos;
+    ws.run_rows = runs;
+    ws.run_starts = runs + ws.ntiles * (ws.nbins + 1);
+    SegMap sm{};
+    if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 || ws.nbins > 511 ||
+        !runs_as_columns(ws) || !ws.lad_u || ws.lad_hb != 0 || !mp.p2 ||
+        // (the store policies compiled in below are the product's only while
+        // the tiles fit the Infinity Cache, choose_pass1_kernel)
+        ws.ntiles * (uint64_t)4096 * 8 > kInfinityCacheBytes)
+        return -22;
+    constexpr int kWgs = pass1_wgs_per_cu(512, false, 511);
+    const unsigned grid1 = pass1_grid(ws.ntiles, device_cu_count(), kWgs);
+    const size_t rounds = (ws.ntiles + grid1 - 1) / grid1;
+    // a stamp per loop iteration and one for the epilogue
+    if (rounds + 1 > (size_t)(kEdgeStamps1 - kEdge1Tile0)) return -22;
+    if ((size_t)grid1 * kEdgeStamps1 + ws.nbins * kEdgeStamps2 > stamps_cap) return -28;
+    int dev = 0, khz = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess)
+        return -5;
+    k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), 0,
+               pass1_wt(1, KEYS_PACKED) ? kStoreWT : kStorePlain, false, pass1_prio_of(kPrioHash, 1), 1, true>
+        <<<grid1, 512, 0, s>>>(ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, reinterpret_cast<uint16_t *>(stamps));
+    if (hipGetLastError() != hipSuccess) return -5;
+    const StackTable st = ladder0_table(mp, ws);
+    const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
+    const hipError_t e = launch_apply_g<kApplyBuildL, 4, 4096, 1, 1, 1, false, 0, 0, true>(
+        ws, mp.m, words, nw32, 0, reinterpret_cast<uint8_t *>(stamps + (size_t)grid1 * kEdgeStamps1), st, s);
+    out4[0] = (int)grid1;
+    out4[1] = (int)ws.nbins;
+    out4[2] = (int)rounds;
+    out4[3] = khz;
+    return e == hipSuccess ? 0 : -5;
+}
+
 // Phases of the product's partition build (tools/ubench.py part, p1ab):
 // 0 = pass 1 as the product launches it, 1 = pass 2 as the product launches
 // it over variant 0's output; 5001 / 5003 = pass-1 shapes (MINW waves per
@@ -636,12 +731,15 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
 #define UB_PIPE(A)                                                                                \
     case 5500 + A: {                                                                             \
         SegMap sm{};                                                                             \
+        /* (tiles within the Infinity Cache: the store policy compiled in here is the */         \
+        /* product's only there, choose_pass1_kernel) */                                         \
         if (pass1_plan(mp, ws, false, &sm) != kModLadder0R || ws.tile_keys != 4096 ||           \
-            ws.nbins > 511 || !runs_as_columns(ws))                                              \
+            ws.nbins > 511 || !runs_as_columns(ws) ||                                            \
+            ws.ntiles * (uint64_t)4096 * 8 > kInfinityCacheBytes)                                \
             return -22;                                                                          \
         constexpr int kWgs = pass1_wgs_per_cu(512, false, 511);                                  \
-        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), A, false, false, \
-                   pass1_prio_of(kPrioHash, 1), 1>                                               \
+        k_part_bin<KEYS_PACKED, false, true, 512, kModLadder0R, 511, pass1_min_waves(512, kWgs), A,           \
+                   pass1_wt(1, KEYS_PACKED) ? kStoreWT : kStorePlain, false, pass1_prio_of(kPrioHash, 1), 1>  \
             <<<pass1_grid(ws.ntiles, device_cu_count(), kWgs), 512, 0, s>>>(                     \
                 ks, mp, ws.pos, ws.run_starts, sm, ws.ntiles, nullptr);                          \
         e = hipGetLastError();                                                                   \

@@ -279,6 +279,96 @@ def p1_tail(m=167_772_160, reps=50):
         torch.cuda.empty_cache()
 
 
+def edges(n=16_777_216, bpe=10.0, reps=7):
+    """The edges of the C2 build's two kernels from wall_clock64() stamps
+    (ubench_edges: k_part_bin's and k_part_apply's STAMP, both kernels in one
+    stream after a warm-up of unstamped builds), per repetition and as
+    medians, in microseconds:
+      p1_third_us      pass 1's time with at most a third of its workgroups
+                       still running (one per CU or fewer on average)
+      p1_idle_wg_us    the mean of (last end - a workgroup's end)
+      p1/p2_end_spread first to last workgroup end of each pass; for pass 1
+                       also how long some CU runs fewer than three workgroups
+      p2_first_vec_us  pass 2's workgroup start to its first entry vector
+                       (median and max over workgroups); p2_staged_us: to
+                       the end of the staging barrier
+      boundary_us      pass 1's last stamp to pass 2's first: the kernel
+                       boundary with its flush
+      p2_writeout_us   pass 2's write-out (median over workgroups)"""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "cs265-lsm-tree_amd"))
+    import bloomhip as bh
+    LIB.ubench_edges.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64] + [ctypes.c_void_p] * 4 + \
+        [ctypes.c_size_t] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    LIB.ubench_edges.restype = ctypes.c_int
+    keys = torch.from_numpy(bh.gen_puts(13141, n)).cuda()
+    m = bh.m_bits(n, bpe)
+    geo = np.zeros(4, dtype=np.uint64)
+    assert LIB.ubench_part_geometry(n, m, geo.ctypes.data) == 0
+    nbins, _, tk, ntiles = (int(x) for x in geo)
+    pos = torch.empty(ntiles * tk, dtype=torch.int64, device="cuda")
+    runs = torch.empty(ntiles * (nbins + 1) * 2, dtype=torch.int32, device="cuda")
+    words = torch.zeros((m + 63) // 64 * 2, dtype=torch.int32, device="cuda")
+    lay = np.zeros(2, dtype=np.int32)
+    LIB.ubench_edge_layout(ctypes.c_void_p(lay.ctypes.data))
+    S1, S2 = int(lay[0]), int(lay[1])  # kEdgeStamps1, kEdgeStamps2
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    stamps = torch.zeros(3 * cus * S1 + nbins * S2, dtype=torch.int64, device="cuda")
+    s = torch.cuda.current_stream()
+    out4 = np.zeros(4, dtype=np.int32)
+
+    def plain(v):
+        return LIB.ubench_part(v, keys.data_ptr(), n, m, pos.data_ptr(), runs.data_ptr(), words.data_ptr(),
+                               s.cuda_stream, pos.numel(), runs.numel())
+
+    def stamped():
+        return LIB.ubench_edges(keys.data_ptr(), n, m, pos.data_ptr(), runs.data_ptr(), words.data_ptr(),
+                                s.cuda_stream, pos.numel(), runs.numel(), stamps.data_ptr(), stamps.numel(),
+                                out4.ctypes.data)
+    assert plain(0) == 0 and plain(1) == 0
+    torch.cuda.synchronize()
+    ref = words.clone()
+    rows = []
+    for rep in range(reps):
+        for _ in range(20):  # warm: the product's own two launches
+            plain(0)
+            plain(1)
+        stamps.zero_()
+        rc = stamped()
+        assert rc == 0, rc
+        torch.cuda.synchronize()
+        assert torch.equal(words, ref), "the stamped build's bitmap differs"
+        g1, g2, rounds, khz = (int(x) for x in out4)
+        us = 1e3 / khz
+        st = stamps.cpu().numpy()
+        a = st[:g1 * S1].reshape(g1, S1).astype(np.float64) * us
+        b = st[g1 * S1:g1 * S1 + g2 * S2].reshape(g2, S2).astype(np.float64) * us
+        t0 = a[:, 0].min()
+        e1 = np.sort(a[:, 1])
+        nt = (a[:, 2:] > 0).sum(axis=1)  # tile stamps of each workgroup (loop iterations + epilogue)
+        last_tile = np.array([a[i, 2 + nt[i] - 1] - a[i, 2 + nt[i] - 2] for i in range(g1)])
+        d = {"op": "build edges", "rep": rep, "grid1": g1, "grid2": g2, "rounds": rounds, "clock_khz": khz,
+             "p1_us": e1[-1] - t0, "p1_start_spread_us": a[:, 0].max() - t0,
+             "p1_end_spread_us": e1[-1] - e1[0],
+             "p1_third_us": e1[-1] - e1[max(g1 - g1 // 3 - 1, 0)],
+             "p1_idle_wg_us": float((e1[-1] - e1).mean()),
+             "p1_epilogue_us_median": float(np.median(last_tile)),
+             "boundary_us": b[:, 0].min() - e1[-1],
+             "p2_us": b[:, 4].max() - b[:, 0].min(), "p2_start_spread_us": b[:, 0].max() - b[:, 0].min(),
+             "p2_end_spread_us": b[:, 4].max() - b[:, 4].min(),
+             "p2_staged_us_median": float(np.median(b[:, 1] - b[:, 0])),
+             "p2_first_vec_us_median": float(np.median(b[:, 2] - b[:, 0])),
+             "p2_first_vec_us_max": float((b[:, 2] - b[:, 0]).max()),
+             "p2_walk_us_median": float(np.median(b[:, 3] - b[:, 2])),
+             "p2_writeout_us_median": float(np.median(b[:, 4] - b[:, 3])),
+             "both_us": b[:, 4].max() - t0}
+        d = {k: (round(v, 2) if isinstance(v, float) else v) for k, v in d.items()}
+        rows.append(d)
+        print(json.dumps(d), flush=True)
+    med = {k: round(float(np.median([r[k] for r in rows])), 2) for k in rows[0] if k.endswith("_us") or "_us_" in k}
+    print(json.dumps({"op": "build edges", "median_of": reps, **med}), flush=True)
+
+
 def stack_ablation(levels_sel=(0, 1, 2, 3, 4)):
     """The stacked C3 probe by phase (ubench_stack variants), and pass 2 with
     its result stores or 4 of its 5 member reads removed."""
@@ -634,6 +724,8 @@ def main():
         return p1_ab([5413], m=512_000_000)
     if len(sys.argv) > 1 and sys.argv[1] == "p1tail":
         return p1_tail()
+    if len(sys.argv) > 1 and sys.argv[1] == "edges":
+        return edges()
     if len(sys.argv) > 1 and sys.argv[1] == "part":
         return part_phases()
     if len(sys.argv) > 1 and sys.argv[1] == "part_c5":
