@@ -70,9 +70,20 @@ struct ApplyWalk {
     int chains;  // 0: the batch walk; 1 or 2: independent lane groups, chains per group
     int vecs;    // 16-B vectors per lane and step
     bool redir;  // a load past the run's end goes to the group's first vector
+    bool lean;   // the build's one-vector group walk on 32-bit offsets (k_part_apply's LEAN)
 };
 inline bool operator==(const ApplyWalk &a, const ApplyWalk &b) {
-    return a.g == b.g && a.chains == b.chains && a.vecs == b.vecs && a.redir == b.redir;
+    return a.g == b.g && a.chains == b.chains && a.vecs == b.vecs && a.redir == b.redir && a.lean == b.lean;
+}
+
+// Whether the lean loop can address a batch: a lane's tile is a signed 32-bit
+// byte offset into the sorted tiles that steps one workgroup's worth of tiles
+// (256 at G = 4) past either end, and its bounds a 32-bit byte offset into
+// the segment's row of the run table.
+inline bool apply_offsets_fit32(size_t tile_keys, size_t nbins, size_t ntiles) {
+    const uint64_t tile_bytes = ((uint64_t)ntiles + 2 * 256) * tile_keys * 8;
+    const uint64_t table_bytes = (uint64_t)ntiles * (nbins + 1) * 4;
+    return tile_bytes < (1ull << 31) && table_bytes < (1ull << 31);
 }
 
 // The walk pass 2 takes for a batch of ntiles tiles of tile_keys keys sorted
@@ -117,6 +128,17 @@ inline ApplyWalk choose_apply_walk(int mode, size_t tile_keys, size_t nbins, siz
     // 192.5 -> 173.6 us, tools/ubench.py p2ab_c5; C2's 128 MiB equal either
     // way, so it keeps one vector)
     if (from_hbm) return {4, 1, 2, true};
+    // tiles from the Infinity Cache, runs of a step or more (C2, the f = 10
+    // build, the general remainder): the same walk on the lean loop
+    // (k_part_apply's LEAN: 65-67 -> 49.5 VALU per step at C2).  The f = 10
+    // build 0.1114 -> 0.1065 ms; C2 0.0773-0.0775 -> 0.0770-0.0771 ms, the
+    // median below the parent's fastest run in both orders, its slowest not;
+    // m = 100,000,007 equal; pass 2 alone, re-reading the same tiles, equal
+    // (31.3 against 31.5 us): the walk is bound by its loads and LDS ORs more
+    // than by its instructions (profiles/pass2_loop/README.md).  A batch the
+    // loop's 32-bit offsets cannot address (none that fits the Infinity
+    // Cache) keeps the loop below.
+    if (apply_offsets_fit32(tile_keys, nbins, ntiles)) return {4, 1, 1, false, true};
     return {4, 1, 1, false};
 }
 
@@ -169,7 +191,8 @@ __device__ __forceinline__ uint32_t stack_bits(const uint32_t *seg, uint32_t o,
 }
 
 template <int MODE, int G, int TILE_KEYS, int BLOCK = kApplyBlock, int DEPTH = kApplyDepth,
-          int CHAINS = 0, int VECS = 1, bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false>
+          int CHAINS = 0, int VECS = 1, bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false,
+          bool LEAN = false>
 __global__ void __launch_bounds__(BLOCK) k_part_apply(
     const uint64_t *__restrict__ pos, const uint32_t *__restrict__ run_starts, int ntiles,
     int nbins, uint32_t seg_bits, uint64_t m, uint32_t *__restrict__ words, uint64_t nw32,
@@ -583,7 +606,97 @@ __global__ void __launch_bounds__(BLOCK) k_part_apply(
     };
 
     static_assert(VECS == 1 || VECS == 2, "vectors per lane and step");
-    if constexpr (CHAINS == 1 && VECS == 1) {
+    if constexpr (LEAN) {
+        // The one-vector group walk below with the per-step bookkeeping cut
+        // down (choose_apply_walk: builds whose tiles and run table are
+        // addressed by 32-bit byte offsets; profiles/pass2_loop/README.md):
+        //  - a lane's tile is the byte offset tb of data tile rt(t) in pos
+        //    (negative once t >= ntiles), its vector the offset tb | vi << 4
+        //    from the uniform base, its bounds at tb >> (kTileShift - 2) in
+        //    the segment's row: no 64-bit address is built per step;
+        //  - the lane's first entry 6 vi is one 24-bit multiply, the run mask
+        //    two saturating subtracts, a min, a shift and a bit-field
+        //    extract, and the group is done with its run when the entries
+        //    left from the lane's first, n, are at most those of the group's
+        //    step from this lane on (c = 6 (G - sub));
+        //  - the mask is taken before the state moves on, so the step keeps
+        //    no copy of the old state, and the body is written twice with
+        //    the two vector registers swapped: the next vector lands where
+        //    the next half reads it, and no step waits for a load it issued
+        //    itself (the ORs wait for the vector of the step before, the
+        //    tile change for the bounds of the step before).
+        // Lanes past the last tile (tb < 0) stay where they are, re-read
+        // tile 0 and apply nothing.
+        static_assert(!PROBE && CHAINS == 1 && VECS == 1 && !REDIR && !STAMP, "the build's one-vector group walk");
+        static_assert(TILE_KEYS == 4096 || TILE_KEYS == 8192, "tiles of 2^15 or 2^16 bytes");
+        constexpr int kGroupsPerWave = 64 / G;
+        constexpr int kTileShift = TILE_KEYS == 4096 ? 15 : 16;  // log2 of a tile's bytes
+        constexpr int32_t kQB = (kGroupsPerWave * (BLOCK / 64)) << kTileShift;  // Q tiles, in bytes
+        const char *tiles = reinterpret_cast<const char *>(pos);
+        const char *row = reinterpret_cast<const char *>(run_starts + (size_t)b * ntiles);
+        // packed bounds of the tile at byte offset x (a tile past the end: tile 0's, never applied)
+        auto bnd_off = [&](int32_t x) -> uint32_t { return (uint32_t)(max(x, 0) >> (kTileShift - 2)); };
+        auto bnd = [&](int32_t x) -> uint32_t { return *reinterpret_cast<const uint32_t *>(row + bnd_off(x)); };
+        auto ldv = [&](int32_t x, uint32_t vi) -> uint4 {
+            return *reinterpret_cast<const uint4 *>(tiles + ((uint32_t)max(x, 0) + (min(vi, kLastVec) << 4)));
+        };
+        auto first_vec = [&](uint32_t pk) -> uint32_t { return (pk & 0xFFFFu) / 6u + sub; };
+        auto or6 = [&](const uint4 &v, uint32_t vm) {
+            const uint32_t e[6] = {v.x & kEntryMask, __builtin_amdgcn_alignbit(v.y, v.x, 21) & kEntryMask,
+                                   v.y >> 10,        v.z & kEntryMask,
+                                   __builtin_amdgcn_alignbit(v.w, v.z, 21) & kEntryMask, v.w >> 10};
+#pragma unroll
+            for (int k = 0; k < 6; k++) build_or(MODE == kApplyBuildL ? e[k] : e[k] - base21, vm, k);
+        };
+        const uint32_t c = 6u * ((uint32_t)G - sub);
+        int32_t tb = (ntiles - 1 - (wave * kGroupsPerWave + tl)) * (1 << kTileShift);
+        uint32_t r = bnd(tb), rn = bnd(tb - kQB);
+        uint32_t vi = first_vec(r);
+        uint4 va = ldv(tb, vi), vb;
+        // one step: the vector in cur is applied, the next one loaded into nxt
+        auto step = [&](const uint4 &cur, uint4 &nxt) {
+            const bool alive = tb >= 0;
+            const uint32_t e = __umul24(vi, 6u);
+            const uint32_t lo = __builtin_elementwise_sub_sat(r & 0xFFFFu, e);
+            const uint32_t n = __builtin_elementwise_sub_sat(r >> 16, e);
+            uint32_t vm = __builtin_amdgcn_ubfe(63u << lo, 0u, min(n, 6u));
+            // (the mask is final before the bounds change: scheduled after the
+            // next load it kept a copy of the old bounds alive, two moves a step)
+            asm volatile("" : "+v"(vm), "+v"(r));
+            vi += G;
+            if (alive && n <= c) {
+                tb -= kQB;
+                // r = rn, made before the lookahead's register takes its load
+                // (hoisted above the copy, the load went to a second register
+                // and the two swapped with a move a step)
+                asm volatile("v_mov_b32 %0, %1" : "=v"(r), "+v"(rn));
+                vi = first_vec(r);
+            }
+            // The lookahead's bounds are loaded by every lane, a lane that
+            // stays on its tile re-reading the ones it has: under the tile
+            // change's branch the load may or may not have been issued, and
+            // the wait for the current vector then had to be the one that
+            // leaves a single load in flight, i.e. it waited for the bounds
+            // just asked for, a memory round trip per step.  Two loads per
+            // step, always: that wait leaves both in flight.  (The offset is
+            // laundered: the compiler otherwise proves the re-read redundant
+            // and moves the load back under the branch.)
+            uint32_t on = bnd_off(tb - kQB);
+            asm volatile("" : "+v"(on));
+            rn = *reinterpret_cast<const uint32_t *>(row + on);
+            nxt = ldv(tb, vi);
+            if (alive && vm != 0) or6(cur, vm);
+        };
+        // The wave leaves when none of its lanes has a tile, tested once per
+        // two steps: the second step of a pair that was not needed applies
+        // nothing (no lane is alive).  One exit also keeps the loop's only
+        // waits the ones for a vector about to be used: with an exit after
+        // either step the compiler waited for every load at the loop's head.
+        while (__ballot(tb >= 0) != 0) {
+            step(va, vb);
+            step(vb, va);
+        }
+    } else if constexpr (CHAINS == 1 && VECS == 1) {
         // Independent lane groups: group q (G lanes) walks tiles q, q + Q,
         // q + 2Q, ... one step (G vectors) per iteration, moving to its next
         // tile as soon as its run ends, so no group waits for the longest run
@@ -911,7 +1024,7 @@ inline void stack_stride(size_t nbins, uint32_t seg_words, size_t lds, StackTabl
 // Launches pass 2 (build or probe) with S/8 bytes of dynamic LDS (> 64 KiB
 // must be opted into per kernel).
 template <int MODE, int G, int TK, int DEPTH = kApplyDepth, int CHAINS = 0, int VECS = 1,
-          bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false>
+          bool REDIR = false, int NF = 0, int LK = 0, bool STAMP = false, bool LEAN = false>
 hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *words,
                           uint64_t nw32, int merge, uint8_t *res, const StackTable &st,
                           hipStream_t stream) {
@@ -922,7 +1035,7 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     // instantiation from the code object, and the launch refused otherwise.
     static const bool lds_ok = [] {
         const void *fn = reinterpret_cast<const void *>(
-            &k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP>);
+            &k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP, LEAN>);
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(kStackMaxBits / 8));
         hipFuncAttributes fa{};
@@ -937,7 +1050,7 @@ hipError_t launch_apply_g(const PartitionWorkspace &ws, uint64_t m, uint32_t *wo
     sk.keep_mask = 0;
     if (MODE == kApplyStack && NF < 8 && G == 4) stack_stride(ws.nbins, ws.seg_bits / 32, lds, sk);
     const unsigned grid = sk.seg_stride ? (unsigned)sk.seg_stride : (unsigned)ws.nbins;
-    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP>
+    k_part_apply<MODE, G, TK, kApplyBlock, DEPTH, CHAINS, VECS, REDIR, NF, LK, STAMP, LEAN>
         <<<grid, kApplyBlock, lds, stream>>>(ws.pos, ws.run_starts, (int)ws.ntiles, (int)ws.nbins,
                                              ws.seg_bits, m, words, nw32, merge, res, sk);
     return hipGetLastError();
@@ -1036,6 +1149,9 @@ hipError_t launch_apply_tk(const PartitionWorkspace &ws, uint64_t m, uint32_t *w
     } else if constexpr (MODE == kApplyProbe) {
         APPLY_ON(4, 0, 1, false) APPLY_ON(8, 0, 1, false) APPLY_ON(16, 0, 1, false) APPLY_ON(32, 0, 1, false)
     } else {
+        if (w == ApplyWalk{4, 1, 1, false, true})  // the lean loop
+            return launch_apply_g<MODE, 4, TK, 1, 1, 1, false, 0, 0, false, true>(ws, m, words, nw32, merge,
+                                                                                  res, st, stream);
         APPLY_ON(4, 1, 1, true) APPLY_ON(4, 1, 2, true) APPLY_ON(4, 1, 1, false)
         APPLY_ON(8, 0, 1, false) APPLY_ON(16, 0, 1, false) APPLY_ON(32, 0, 1, false)
     }

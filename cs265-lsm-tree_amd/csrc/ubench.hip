@@ -502,6 +502,58 @@ extern "C" int ubench_part_walk(int chains, int vecs, int redir, const void *key
     return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -22 : -5;
 }
 
+// The product's pass 1, then pass 2 on the one-vector group walk (G = 4, no
+// redirect) with either of its loops forced: lean = 0 the plain loop, 1 the
+// lean loop on 32-bit offsets (k_part_apply's LEAN), in the geometry's own
+// mode on 4096- or 8192-key tiles; merge: OR into the bitmap in words
+// (tests/test_gpu_pass2_build_loop.py, tools/ubench.py p2ab).  -22: not such
+// a geometry, or a batch the lean loop's offsets cannot address.  Buffers as
+// for ubench_part.
+extern "C" int ubench_part_loop(int lean, int merge, const void *keys, size_t n, uint64_t m,
+                                uint64_t *pos, uint32_t *runs, uint32_t *words, void *stream,
+                                size_t pos_cap, size_t runs_cap) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const KeySpan ks{reinterpret_cast<const char *>(keys), n, 4, KEYS_PACKED};
+    const ModParams mp = make_mod_params(m);
+    PartitionWorkspace ws{};
+    int mode = 0;
+    if (n == 0) return -22;
+    if (!build_plan(n, m, device_cu_count(), &ws, &mode)) return -34;
+    if (ws.ntiles * ws.tile_keys > pos_cap || 2 * ws.ntiles * (ws.nbins + 1) > runs_cap) return -28;
+    if (lean && !apply_offsets_fit32(ws.tile_keys, ws.nbins, ws.ntiles)) return -22;
+    ws.pos = pos;
+    ws.run_rows = runs;
+    ws.run_starts = runs + ws.ntiles * (ws.nbins + 1);
+    hipError_t e = launch_part_bin(ks, mp, ws, s);
+    if (e != hipSuccess) {
+        fprintf(stderr, "ubench_part_loop: pass 1: %s\n", hipGetErrorString(e));
+        return -5;
+    }
+    const StackTable st = mode == kApplyBuildL ? ladder0_table(mp, ws) : StackTable{};
+    const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
+    e = hipErrorInvalidValue;  // no such geometry
+#define UB_ON(MODE, TK)                                                                           \
+    if (mode == MODE && ws.tile_keys == TK)                                                       \
+        e = lean ? launch_apply_g<MODE, 4, TK, 1, 1, 1, false, 0, 0, false, true>(ws, mp.m, words, nw32, merge, nullptr, st, s) \
+                 : launch_apply_g<MODE, 4, TK, 1, 1, 1, false>(ws, mp.m, words, nw32, merge, nullptr, st, s);
+    UB_ON(kApplyBuildL, 4096) UB_ON(kApplyBuildL, 8192) UB_ON(kApplyBuild, 4096) UB_ON(kApplyBuild, 8192)
+#undef UB_ON
+    if (e != hipSuccess) fprintf(stderr, "ubench_part_loop: pass 2: %s\n", hipGetErrorString(e));
+    return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -22 : -5;
+}
+
+// choose_apply_walk itself, with no device call: out6 = G, CHAINS, VECS,
+// REDIR, LEAN for a pass 2 of `mode` (kApply*) over ntiles tiles of tile_keys
+// keys sorted into nbins segments, then whether the lean loop's 32-bit
+// offsets can address that batch (apply_offsets_fit32)
+// (tests/test_host_pass2_loop.py).
+extern "C" void ubench_apply_walk(int mode, size_t tile_keys, size_t nbins, size_t ntiles, int *out6) {
+    const ApplyWalk w = choose_apply_walk(mode, tile_keys, nbins, ntiles);
+    const int out[6] = {w.g, w.chains, w.vecs, (int)w.redir, (int)w.lean,
+                        (int)apply_offsets_fit32(tile_keys, nbins, ntiles)};
+    std::copy(out, out + 6, out6);
+}
+
 // The product's build on a forced pass-1 grid: the kernel choose_pass1_kernel
 // gives (store policy included), launched on min(grid, tiles) persistent
 // workgroups, then the product's pass 2.  A small grid runs the tile loop of
@@ -658,9 +710,9 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
             break;
         }
         // Pass 2 of plan_build's one-member ladder (C2, C5) over variant 0's
-        // output at G = 4: 2401 the product's C2 walk (1, 1, plain), 2413 the
-        // product's C5 walk (1, 2, redirected), 2417 that on two chains
-        case 2401: case 2413: case 2417: {
+        // output at G = 4: 2401 the C2 walk (1, 1, plain) on the plain loop, 2413
+        // the product's C5 walk (1, 2, redirected), 2417 that on two chains
+        case 2401: case 2413: case 2417: case 2420: {
             if (!ws.lad_u || ws.lad_hb != 0 || !mp.p2) return -22;
             const StackTable st = ladder0_table(mp, ws);
             const uint64_t nw32 = ((mp.m + 63) / 64) * 2;
@@ -672,6 +724,12 @@ extern "C" int ubench_part(int variant, const void *keys, size_t n, uint64_t m, 
                        : launch_apply_g<kApplyBuildL, 4, 8192, 1, C, NV, R>(ws, mp.m, words, nw32, 0, nullptr, st, s);
             UB_WALK(2401, 1, 1, false) UB_WALK(2413, 1, 2, true) UB_WALK(2417, 2, 2, true)
 #undef UB_WALK
+            // 2420: 2401's walk on the lean loop (the product's at C2)
+            if (variant == 2420 && apply_offsets_fit32(tk, ws.nbins, ws.ntiles))
+                e = tk == 4096 ? launch_apply_g<kApplyBuildL, 4, 4096, 1, 1, 1, false, 0, 0, false, true>(ws, mp.m, words, nw32, 0, nullptr, st, s)
+                               : launch_apply_g<kApplyBuildL, 4, 8192, 1, 1, 1, false, 0, 0, false, true>(ws, mp.m, words, nw32, 0, nullptr, st, s);
+            else if (variant == 2420)
+                return -22;
             break;
         }
         // 5100 + ABL: the product's C2 pass 1 (plan_build's one-member

@@ -5,7 +5,9 @@
 labels renumbered) and the -Rpass-analysis=kernel-resource-usage lines.
 Prints one line per kernel (same / DIFF, instruction lines, a digest of the
 stream, registers, spills, LDS, occupancy) and the counts per unit.  Kernels
-are paired by their mangled names.
+are paired by their mangled names; a k_part_apply whose last template
+argument (LEAN) is false pairs with the parent's kernel that has no such
+argument.
 Usage: python tools/isa_cmp.py PARENT_OBJ NEW_OBJ UNIT..."""
 import hashlib
 import re
@@ -73,6 +75,16 @@ def resources(path):
     return res
 
 
+def without_lean(names, parent):
+    """A k_part_apply of the new side whose last template argument, LEAN, is
+    false, under the name it has at a parent that has no such parameter."""
+    out = {}
+    for k, v in names.items():
+        old = re.sub(r"(k_part_applyI\w*?)Lb0E(EEvPKmPKjiijmPjmiPhNS_10StackTableE)$", r"\1\2", k)
+        out[old if old != k and old in parent and k not in parent else k] = v
+    return out
+
+
 def main():
     pa, nb = sys.argv[1], sys.argv[2]
     tot = [0, 0, 0]
@@ -81,6 +93,7 @@ def main():
         kb = kernels(f"{nb}/{unit}-hip-amdgcn-amd-amdhsa-gfx950.s")
         ra = resources(f"{pa}/resource_usage_{unit}.txt")
         rb = resources(f"{nb}/resource_usage_{unit}.txt")
+        kb, rb = without_lean(kb, ka), without_lean(rb, ka)
         differing = 0
         dm = demangle(sorted(set(ka) | set(kb)))
         print(f"== {unit}: kernels at the parent {len(ka)}, now {len(kb)}; "

@@ -157,8 +157,9 @@ def p2_ab(variants, n=16_777_216, bpe=10.0, rounds=3, reps=50):
     all over the product's pass-1 output; each variant's bitmap must equal
     the product's.  The variants are ubench_part's walks at G = 4 by
     k_part_apply's (CHAINS, VECS, REDIR).  On plan_build's one-member ladder
-    (C2, C5): 2401 (1, 1, plain), 2413 (1, 2, redirected), 2417 (2, 2,
-    redirected).  On super-tiles (C4): 2522 (1, 1, redirected), 2503 (1, 2,
+    (C2, C5): 2401 (1, 1, plain) on the plain loop, 2420 the same walk on
+    the lean loop (k_part_apply's LEAN; `p2ab` times both by default), 2413
+    (1, 2, redirected), 2417 (2, 2, redirected).  On super-tiles (C4): 2522 (1, 1, redirected), 2503 (1, 2,
     redirected), 2507 (2, 2, redirected), 2523 (1, 2, redirected) at two
     lanes per tile.  With no applicable variant it times the product's
     pass 2 alone (UBENCH_LIB picks the library: an A/B of two builds)."""
@@ -698,6 +699,8 @@ def main():
         return p1_ab(vs)
     if len(sys.argv) > 1 and sys.argv[1].startswith("p2ab"):
         vs = [int(v) for v in os.environ.get("UB_VARIANTS", "").split(",") if v]
+        if not vs and sys.argv[1] == "p2ab":
+            vs = [2401, 2420]  # the build's plain and lean loops
         size = {"p2ab": (16_777_216, 10.0, 50), "p2ab_c5": (67_108_864, 10.0, 20),
                 "p2ab_c4": (268_435_456, 12.0, 5)}[sys.argv[1]]
         return p2_ab(vs, *size)
