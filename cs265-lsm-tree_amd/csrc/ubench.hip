@@ -370,6 +370,21 @@ extern "C" int ubench_walk_choice(size_t n, int nf, const uint64_t *ms, int cu_c
     return 0;
 }
 
+// The same for a one-filter partitioned probe (launch_probe_partitioned) of n
+// keys against a filter of m bits: plan_segments' geometry, tiles as
+// partition_buffers sizes them, choose_apply_walk(kApplyProbe).  No device
+// call.  out7 as above (tests/test_gpu_probe_walks.py asserts G from it).
+extern "C" int ubench_probe_walk_choice(size_t n, uint64_t m, int cu_count, int *out7) {
+    PartitionWorkspace ws{};
+    if (!plan_segments(m, cu_count, &ws)) return -34;
+    ws.tile_keys = choose_tile_keys(ws.nbins);
+    ws.ntiles = (n + ws.tile_keys - 1) / ws.tile_keys;
+    const ApplyWalk w = choose_apply_walk(kApplyProbe, ws.tile_keys, ws.nbins, ws.ntiles);
+    const int out[7] = {kApplyProbe, (int)ws.tile_keys, (int)ws.nbins, w.g, w.chains, w.vecs, (int)w.redir};
+    std::copy(out, out + 7, out7);
+    return 0;
+}
+
 // The pass-1 kernel the product chooses (choose_pass1_kernel) on a device of
 // cu_count CUs, with no device call, for n keys at `stride` bytes (4: packed,
 // 8: entry_t, both from a 16-B aligned base; else strided) and m bits:

@@ -329,6 +329,39 @@ WALK_ROWS = [
     # 8192 keys) against one tile more, on C5's geometry
     (33_554_432, [671_088_640], (BUILD_L, 8192, 512, 4, 1, 1, 0)),
     (33_554_433, [671_088_640], (BUILD_L, 8192, 512, 4, 1, 2, 1)),
+    # The stacks of tests/test_gpu_probe_walks.py, 513 tiles ending in 777 keys
+    # (no member set is a ladder: the odd parts differ or are no divisor of 255).
+    # 256,000 * 10^i, i = 1..3: m_max = 2^14 * 5^6, three members share 160 KiB:
+    # w <= 436,906 bits, and the widest divisor of m_max that is a multiple of
+    # 128 is 2^14 * 25 = 409,600: 625 segments, 8192-key tiles, runs of 39.
+    (4_195_081, [256_000_000, 25_600_000, 2_560_000], (STACK, 8192, 625, 4, 1, 1, 0)),
+    # 3 << 26 with 1 << 15: w <= the smallest member, so w = 2^15 and 6,144
+    # segments, more than super-tiles sort (4,095): 8192-key tiles, runs of 4
+    # entries, the short-run walk with the redirect
+    (4_195_081, [3 << 26, 1 << 15], (STACK, 8192, 6144, 4, 1, 1, 1)),
+    # eight members under 3 << 20: w <= 2^16, the widest w with a segment per
+    # CU is 3 << 12 (256 segments): 4096-key tiles, runs of 48
+    (2_097_929, [3 << 20, 1 << 20, 3 << 18, 1 << 18, 1 << 19, 3 << 17, 1 << 17, 1 << 16],
+     (STACK, 4096, 256, 4, 1, 1, 0)),
+    # 12,800 = 100 * 128 bits: even the narrowest w, 128 bits, gives fewer
+    # segments than CUs, so that one: 100 segments, runs of 122 on 4096-key
+    # tiles, the batch walk at G = 8
+    (2_097_929, [12_800, 6_400, 3_200], (STACK, 4096, 100, 8, 0, 1, 0)),
+]
+
+# The same for a one-filter partitioned probe (ubench_probe_walk_choice:
+# plan_segments, choose_tile_keys, choose_apply_walk(kApplyProbe)): always the
+# batch walk, G from the run length 3 * tile keys / segments.  Rows: (n keys, m)
+# -> as above.  5 << 25: 256 segments of 4096-key tiles, runs of 48; 5 << 27:
+# 512 segments (PASS1_ROWS' C5 probe) of 8192-key tiles, runs of 48; 100,000 /
+# 50,000 / 20,000 bits: 98 / 49 / 20 segments of 1,024 bits (the builds'
+# rows above), runs of 125 / 250 / 614.
+PROBE_WALK_ROWS = [
+    (4_195_081, 5 << 25, (PROBE, 4096, 256, 4, 0, 1, 0)),
+    (8_389_385, 5 << 27, (PROBE, 8192, 512, 4, 0, 1, 0)),
+    (2_097_929, 100_000, (PROBE, 4096, 98, 8, 0, 1, 0)),
+    (1_049_353, 50_000, (PROBE, 4096, 49, 16, 0, 1, 0)),
+    (525_065, 20_000, (PROBE, 4096, 20, 32, 0, 1, 0)),
 ]
 
 
@@ -403,6 +436,20 @@ PASS1_ROWS = [
     # deferred nor nt with the slot plane
     (16_777_216, 3 << 26, 1, 4, (0, 512, PACKED, 1, 1, P2, 511, 2, 0, 0, 512)),
     (16_777_216, 671_088_640, 1, 4, (0, 1024, PACKED, 1, 1, P2, 1023, 1, 0, 0, 256)),
+    # the single probes of tests/test_gpu_probe_walks.py (PROBE_WALK_ROWS).
+    # 5 << 25 (t = 25 >= 21: kModP2) on 256 segments of 4096-key tiles, two
+    # 512-thread workgroups per CU: 2C + 1 tiles ending in one key and 2C + 2
+    # ending in 4095 keys give a workgroup a second tile (grid 512); entry_t keys
+    (2_097_153, 5 << 25, 1, 4, (0, 512, PACKED, 1, 1, P2, 511, 2, 0, 0, 512)),
+    (2_105_343, 5 << 25, 1, 4, (0, 512, PACKED, 1, 1, P2, 511, 2, 0, 0, 512)),
+    (2_097_929, 5 << 25, 1, 8, (0, 512, ENTRY, 1, 1, P2, 511, 2, 0, 0, 512)),
+    # 5 << 27 at 1,025 tiles of 8192 keys; the filters of 98, 49 and 20
+    # segments (no p2 form: the general remainder) at 513, 257 and 129 tiles,
+    # of which only the first outnumber the 512 resident workgroups
+    (8_389_385, 5 << 27, 1, 4, (0, 1024, PACKED, 1, 1, P2, 1023, 1, 0, 0, 256)),
+    (2_097_929, 100_000, 1, 4, (0, 512, PACKED, 1, 1, FAST, 511, 2, 0, 0, 512)),
+    (1_049_353, 50_000, 1, 4, (0, 512, PACKED, 1, 1, FAST, 511, 2, 0, 0, 257)),
+    (525_065, 20_000, 1, 4, (0, 512, PACKED, 1, 1, FAST, 511, 2, 0, 0, 129)),
 ]
 
 
@@ -444,6 +491,24 @@ def test_pass2_walk_choice(n, ms, want):
     out = np.zeros(7, dtype=np.int32)
     assert ub.ubench_walk_choice(n, len(ms), sizes.ctypes.data, 256, out.ctypes.data) == 0
     assert tuple(int(x) for x in out) == want
+
+
+def _probe_walk_choice(n, m):
+    bh.lib()  # torch's HIP runtime first (bloomhip._lib): one runtime per process
+    ub = ctypes.CDLL(os.path.join(os.path.dirname(bh.LIB_PATH), "libbloomhip_ubench.so"))
+    ub.ubench_probe_walk_choice.argtypes = [ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_void_p]
+    out = np.zeros(7, dtype=np.int32)
+    return ub.ubench_probe_walk_choice(n, m, 256, out.ctypes.data), tuple(int(x) for x in out)
+
+
+@pytest.mark.parametrize("n,m,want", PROBE_WALK_ROWS)
+def test_probe_walk_choice(n, m, want):
+    assert _probe_walk_choice(n, m) == (0, want)
+
+
+def test_probe_walk_choice_refusal():
+    """m = 2^40 has no segment geometry (test_pass1_kernel_choice_refusal)."""
+    assert _probe_walk_choice(1_000_000, 1 << 40) == (-34, (0,) * 7)
 
 
 # ---------------------------------------------------------------------------
@@ -573,3 +638,31 @@ def test_stack_pass1_kernel_choice(monkeypatch):
     # one filter is no stack; sizes with no common segment width have no geometry
     assert _stack_pass1_choice(1000, [5 << 25])[0] == -22
     assert _stack_pass1_choice(1000, [1_000_000, 1_000_000])[0] == -34
+
+
+# Pass 1 of the stacked probes of tests/test_gpu_probe_walks.py on 256 CUs, at
+# their 513-tile shapes (WALK_ROWS has the segments and tile keys of each).
+# Rows: (n, member sizes, key stride) -> Pass1Kernel's fields as in PASS1_ROWS.
+# The f = 10 tree on super-tiles: one workgroup per CU, so 513 tiles are a
+# second and a third tile for workgroup 0; 625 segments: MAXB 1023; 6,144
+# segments of 3 << 26 (t = 26: kModP2): only the full capacity 8192 holds them;
+# 256 and 100 segments on 4096-key tiles: 512 threads, MAXB 511, two workgroups
+# per CU with the slot plane (3 << 20 has t = 20 < 21: the general remainder,
+# as 12,800 = 25 << 9); C3's ladder on 8192-key tiles (kModLadder = 3).
+STACK_PASS1_ROWS = [
+    (8_389_385, [512_000_000, 51_200_000, 5_120_000], 4, (1, 1024, PACKED, 1, 1, FAST, 4095, 1, 0, 0, 256)),
+    (4_195_081, [512_000_000, 51_200_000, 5_120_000], 8, (1, 1024, ENTRY, 1, 1, FAST, 4095, 1, 0, 0, 256)),
+    (4_195_081, [256_000_000, 25_600_000, 2_560_000], 4, (0, 1024, PACKED, 1, 1, FAST, 1023, 1, 0, 0, 256)),
+    (4_195_081, [3 << 26, 1 << 15], 4, (0, 1024, PACKED, 1, 1, P2, 8192, 1, 0, 0, 256)),
+    (2_097_929, [3 << 20, 1 << 20, 3 << 18, 1 << 18, 1 << 19, 3 << 17, 1 << 17, 1 << 16], 4,
+     (0, 512, PACKED, 1, 1, FAST, 511, 2, 0, 0, 512)),
+    (2_097_929, [12_800, 6_400, 3_200], 4, (0, 512, PACKED, 1, 1, FAST, 511, 2, 0, 0, 512)),
+    (4_195_081, [655_360 * 4 ** i for i in range(4, -1, -1)], 4, (0, 1024, PACKED, 1, 1, 3, 1023, 1, 0, 0, 256)),
+    (2_097_929, [655_360 * 4 ** i for i in range(4, -1, -1)], 8, (0, 1024, ENTRY, 1, 1, 3, 1023, 1, 0, 0, 256)),
+]
+
+
+@pytest.mark.parametrize("n,ms,stride,want", STACK_PASS1_ROWS)
+def test_stack_pass1_kernel_choice_probe_walk_shapes(monkeypatch, n, ms, stride, want):
+    monkeypatch.delenv("BLOOMHIP_RUN_TABLE", raising=False)
+    assert _stack_pass1_choice(n, ms, stride=stride) == (0, want)
