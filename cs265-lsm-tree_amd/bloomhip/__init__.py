@@ -62,7 +62,10 @@ EXPORTED_SYMBOLS = (
     "bloomhip_gen_workload", "bloomhip_set_batch_run", "bloomhip_set_run_meta",
     "bloomhip_get_run_meta", "bloomhip_route_gets", "bloomhip_route_gets_packed", "bloomhip_save", "bloomhip_load",
     "bloomhip_build_from_run_file", "bloomhip_compact", "bloomhip_clone", "bloomhip_get_batch",
-    "bloomhip_range_batch", "bloomhip_flush_batch",
+    "bloomhip_range_batch", "bloomhip_flush_batch", "bloomhip_flush_cuts",
+    "bloomhip_tree_plan_host", "bloomhip_tree_create", "bloomhip_tree_destroy",
+    "bloomhip_tree_put_batch", "bloomhip_tree_get_batch", "bloomhip_tree_range_batch",
+    "bloomhip_tree_shape", "bloomhip_tree_run",
 )
 
 
@@ -146,6 +149,16 @@ def _lib():
             "bloomhip_compact": (I, [ctypes.POINTER(P), P, I, I, I, P, ctypes.POINTER(SZ), I, P,
                                      I, P]),
             "bloomhip_flush_batch": (I, [P, SZ, I, I, P, ctypes.POINTER(SZ), I, P, I, P]),
+            "bloomhip_flush_cuts": (I, [P, SZ, I, U64, P, SZ, ctypes.POINTER(SZ), I, P]),
+            "bloomhip_tree_plan_host": (I, [P, I, I, U64, P, SZ, ctypes.POINTER(SZ)]),
+            "bloomhip_tree_create": (I, [I, U64, I, I, ctypes.c_float, ctypes.POINTER(P)]),
+            "bloomhip_tree_destroy": (I, [P]),
+            "bloomhip_tree_put_batch": (I, [P, P, SZ, I, ctypes.POINTER(SZ), P]),
+            "bloomhip_tree_get_batch": (I, [P, P, SZ, SZ, I, P, P, I, P]),
+            "bloomhip_tree_range_batch": (I, [P, P, P, SZ, I, P, P, SZ, ctypes.POINTER(SZ), I, P]),
+            "bloomhip_tree_shape": (I, [P, P, PU64]),
+            "bloomhip_tree_run": (I, [P, I, I, ctypes.POINTER(P), ctypes.POINTER(P),
+                                      ctypes.POINTER(SZ)]),
             "bloomhip_save": (I, [P, ctypes.c_char_p]),
             "bloomhip_clone": (I, [P, I, ctypes.POINTER(P)]),
             "bloomhip_load": (I, [ctypes.c_char_p, I, ctypes.POINTER(P)]),
@@ -320,7 +333,8 @@ class BloomFilter:
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            _lib().bloomhip_destroy(self._h)
+            if not getattr(self, "_borrowed", False):  # a view of a tree's run is the tree's
+                _lib().bloomhip_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -708,6 +722,199 @@ def flush_batch(ops, drop_tombstones: bool = False, filter: BloomFilter | None =
                                        filter.device if filter is not None else device,
                                        _stream_ptr(stream)), "bloomhip_flush_batch")
     return out[:n_out.value]
+
+
+# bloomhip_flush_cuts' walk (csrc/bloom_tree.h kTreeCutChunk): one workgroup
+# takes the op stream in chunks of TREE_CUT_CHUNK ops, one per lane; chunk c is
+# ops [c * TREE_CUT_CHUNK, (c + 1) * TREE_CUT_CHUNK).
+TREE_CUT_CHUNK = 1024
+
+
+def _ops_ptr(ops, what: str):
+    dt = str(ops.dtype)
+    if dt not in ("int32", "torch.int32") or len(ops.shape) != 2 or ops.shape[1] != 2:
+        raise ValueError(f"{what} must be an int32 [n, 2] entry_t array (got {dt} {tuple(ops.shape)})")
+    ptr, on_dev, keep = _ptr_of(ops)
+    return ptr, on_dev, keep, _nbytes(keep) // 8
+
+
+def flush_cuts(ops, buffer_max_entries: int, device: int = 0, cuts_cap: int | None = None,
+               stream=None) -> np.ndarray:
+    """Where the reference's buffer of `buffer_max_entries` flushes on `ops`
+    (bloomhip_flush_cuts): ops = entry_t records in arrival order (an int32
+    [n, 2] numpy array or device tensor).  Returns the realised cuts 0 < c_1 <
+    ... < n as np.uint64: segment k is ops[c_{k-1}:c_k], the tail stays in the
+    buffer.  cuts_cap (for tests) limits the output: BloomHipError(ERANGE) with
+    the true count in its `ncuts` when there are more."""
+    ptr, on_dev, keep, n = _ops_ptr(ops, "ops")
+    B = int(buffer_max_entries)
+    cap = (n // B + 1 if B > 0 else 0) if cuts_cap is None else int(cuts_cap)
+    cuts = np.empty(max(cap, 1), dtype=np.uint64)
+    nc = ctypes.c_size_t()
+    rc = _lib().bloomhip_flush_cuts(ptr if n else None, n, on_dev, max(B, 0),
+                                    cuts.ctypes.data if cap else None, cap, ctypes.byref(nc),
+                                    device, _stream_ptr(stream))
+    if rc != OK:
+        err = BloomHipError(rc, "bloomhip_flush_cuts")
+        err.ncuts = nc.value
+        raise err
+    return cuts[:nc.value].copy()
+
+
+def tree_plan(runs_per_level, fanout: int, nflushes: int):
+    """The plan LSMTree.put_batch builds its runs by (bloomhip_tree_plan_host;
+    no GPU needed): from the runs per level before a batch and the number of
+    flushes it makes, the final tree as a list of
+    (level, first_new, n_new, [(old_level, old_index), ...]), level by level,
+    newest first.  BloomHipError(ERANGE) when the reference would die with
+    "No more space in tree"."""
+    shape = np.ascontiguousarray(runs_per_level, dtype=np.uint32)
+    depth = int(shape.size)
+    ln = ctypes.c_size_t()
+    L = _lib()
+    rc = L.bloomhip_tree_plan_host(shape.ctypes.data, depth, int(fanout), int(nflushes), None, 0,
+                                   ctypes.byref(ln))
+    if rc != OK and not (rc == ERANGE and ln.value):
+        raise BloomHipError(rc, "bloomhip_tree_plan_host")
+    flat = np.empty(max(ln.value, 1), dtype=np.int32)
+    _check(L.bloomhip_tree_plan_host(shape.ctypes.data, depth, int(fanout), int(nflushes),
+                                     flat.ctypes.data, ln.value, ctypes.byref(ln)),
+           "bloomhip_tree_plan_host")
+    plan, o = [], 0
+    while o < ln.value:
+        level, first, n_new, n_old = (int(x) for x in flat[o:o + 4])
+        olds = [(int(flat[o + 4 + 2 * j]), int(flat[o + 5 + 2 * j])) for j in range(n_old)]
+        plan.append((level, first, n_new, olds))
+        o += 4 + 2 * n_old
+    return plan
+
+
+class LSMTree:
+    """The reference's LSMTree (src/lsm_tree.h:9-13 for the defaults) with
+    batched ingest: a ``bloomhip_tree`` handle.  After any sequence of
+    put_batch calls it holds exactly the tree the reference holds after the
+    same ops put one by one."""
+
+    def __init__(self, buffer_max_entries: int, depth: int = 5, fanout: int = 10,
+                 bits_per_entry: float = 0.5, device: int = 0):
+        h = ctypes.c_void_p()
+        _check(_lib().bloomhip_tree_create(device, max(int(buffer_max_entries), 0), int(depth),
+                                           int(fanout), float(bits_per_entry), ctypes.byref(h)),
+               "bloomhip_tree_create")
+        self._h = h
+        self.buffer_max_entries = int(buffer_max_entries)
+        self.depth, self.fanout = int(depth), int(fanout)
+        self.bits_per_entry = float(bits_per_entry)
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            _lib().bloomhip_tree_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def put_batch(self, ops, stream=None) -> int:
+        """Puts and deletes in arrival order (int32 [n, 2] entry_t records, a
+        delete carrying VAL_NONE; numpy array or device tensor).  Returns the
+        number of flushes the reference makes on them.  BloomHipError(ERANGE)
+        where it would die with "No more space in tree"; the tree is unchanged
+        then."""
+        ptr, on_dev, keep, n = _ops_ptr(ops, "ops")
+        nf = ctypes.c_size_t()
+        _check(_lib().bloomhip_tree_put_batch(self._h, ptr if n else None, n, on_dev,
+                                              ctypes.byref(nf), _stream_ptr(stream)),
+               "bloomhip_tree_put_batch")
+        return nf.value
+
+    def load(self, path: str) -> int:
+        """LSMTree::load (src/lsm_tree.cpp:296-309): a put per entry_t record
+        of a binary file."""
+        raw = np.fromfile(path, dtype=np.int32)
+        return self.put_batch(raw[:raw.size // 2 * 2].reshape(-1, 2))
+
+    def get(self, keys, n: int | None = None, stride: int = 4, vals=None, found_run=None,
+            stream=None):
+        """Batched GET over the buffer and the runs.  Returns (vals int32[n],
+        found_run int32[n]): VAL_NONE and -1 where no run holds the key (a
+        tombstone's value is passed through); found_run is 0 for the buffer and
+        1 + r for run r in get_run order.  Outputs are host arrays unless
+        device tensors are given."""
+        ptr, on_dev, keep = _keys_ptr(keys, stride)
+        n = _key_count(keep, stride, n)
+        if vals is None and found_run is None:
+            vals = np.empty(n, dtype=np.int32)
+            found_run = np.empty(n, dtype=np.int32)
+        outs = [_out_ptr(x, n * 4, 4, w) if x is not None else (None, None, None)
+                for x, w in ((vals, "vals"), (found_run, "found_run"))]
+        devs = {o[1] for o in outs if o[0] is not None}
+        if len(devs) > 1:
+            raise ValueError("get outputs must be all host or all device buffers")
+        _check(_lib().bloomhip_tree_get_batch(self._h, ptr, n, stride, on_dev, outs[0][0], outs[1][0],
+                                              devs.pop() if devs else 0, _stream_ptr(stream)),
+               "bloomhip_tree_get_batch")
+        return vals, found_run
+
+    def range(self, starts, ends, stream=None):
+        """Batched RANGE: (offsets uint64[nq + 1], entries int32[total, 2]),
+        query q's answer being entries[offsets[q]:offsets[q + 1]] (host arrays)."""
+        sptr, s_dev, skeep = _keys_ptr(starts, 4)
+        eptr, e_dev, ekeep = _keys_ptr(ends, 4)
+        nq = _nbytes(skeep) // 4
+        if _nbytes(ekeep) // 4 != nq:
+            raise ValueError("starts and ends must have one length")
+        if nq and s_dev != e_dev:
+            raise ValueError("starts and ends must be both host or both device buffers")
+        offsets = np.empty(nq + 1, dtype=np.uint64)
+        total = ctypes.c_size_t()
+
+        def call(buf, cap):
+            return _lib().bloomhip_tree_range_batch(self._h, sptr, eptr, nq, s_dev, offsets.ctypes.data,
+                                                    buf, cap, ctypes.byref(total), 0,
+                                                    _stream_ptr(stream))
+
+        _check(call(None, 0), "bloomhip_tree_range_batch")
+        out = np.empty((total.value, 2), dtype=np.int32)
+        if total.value:
+            _check(call(out.ctypes.data, total.value), "bloomhip_tree_range_batch")
+        return offsets, out
+
+    def shape(self):
+        """(runs per level, entries in the buffer)."""
+        rpl = np.zeros(self.depth, dtype=np.uint32)
+        mem = ctypes.c_uint64()
+        _check(_lib().bloomhip_tree_shape(self._h, rpl.ctypes.data, ctypes.byref(mem)),
+               "bloomhip_tree_shape")
+        return [int(x) for x in rpl], mem.value
+
+    def run(self, level: int, index: int = 0):
+        """(entries int32[n, 2] on the host, BloomFilter view) of run `index`
+        (0 = newest) of `level`; level -1 is the buffer as a key-sorted run.
+        The view is the tree's own filter: valid until the next put_batch."""
+        f, e, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        _check(_lib().bloomhip_tree_run(self._h, int(level), int(index), ctypes.byref(f),
+                                        ctypes.byref(e), ctypes.byref(n)), "bloomhip_tree_run")
+        view = BloomFilter._adopt(f, self.device)
+        view._borrowed = True
+        out = np.empty((n.value, 2), dtype=np.int32)
+        if n.value:
+            # a compaction of one run is a copy of it: device to host
+            arr = (ctypes.c_void_p * 1)(e.value)
+            ns = (ctypes.c_size_t * 1)(n.value)
+            got = ctypes.c_size_t()
+            _check(_lib().bloomhip_compact(arr, ns, 1, 1, 0, out.ctypes.data, ctypes.byref(got), 0,
+                                           None, self.device, None), "bloomhip_compact")
+            if got.value != n.value:
+                raise BloomHipError(EIO, "LSMTree.run: the run's keys are not distinct")
+        return out, view
 
 
 # --- workload streams (generator/generator.c restatement) --------------------

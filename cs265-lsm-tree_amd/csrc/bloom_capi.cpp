@@ -26,6 +26,7 @@
 #include "bloom_kernels.h"
 #include "bloom_merge.h"
 #include "bloom_range.h"
+#include "bloom_tree.h"
 
 using namespace bloomhip;
 
@@ -242,6 +243,8 @@ struct Workspace {
     size_t rbuf_bytes[5] = {0, 0, 0, 0, 0};
     uint32_t *fcount = nullptr;  // batched PUT: digit histograms, tile counts, chunk totals
     size_t fcount_bytes = 0;
+    uint32_t *tcut = nullptr;  // flush cuts: prev links, the cut count, the cuts
+    size_t tcut_bytes = 0;
 };
 enum RangeBuf { RBUF_TABLES = 0, RBUF_LARGE = 1, RBUF_ENTRIES = 2, RBUF_SLICES = 3, RBUF_OUT = 4 };
 
@@ -281,7 +284,7 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     for (void **p : {(void **)&w->pos, (void **)&w->runs, (void **)&w->res, (void **)&w->slots,
                      &w->mbuf[0], &w->mbuf[1], (void **)&w->msplit, (void **)&w->mcount,
                      (void **)&w->mkeys, &w->kway, &w->rbuf[0], &w->rbuf[1], &w->rbuf[2], &w->rbuf[3],
-                     &w->rbuf[4], (void **)&w->fcount}) {
+                     &w->rbuf[4], (void **)&w->fcount, (void **)&w->tcut}) {
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
@@ -289,7 +292,7 @@ void free_workspace_buffers(int device, hipStream_t s, Workspace *w) {
     w->h_kept = w->d_kept = nullptr;
     w->pos_bytes = w->runs_bytes = w->res_bytes = w->slots_bytes = 0;
     w->mbuf_bytes[0] = w->mbuf_bytes[1] = w->msplit_bytes = w->mcount_bytes = w->mkeys_bytes = 0;
-    w->kway_bytes = w->fcount_bytes = 0;
+    w->kway_bytes = w->fcount_bytes = w->tcut_bytes = 0;
     for (size_t &b : w->rbuf_bytes) b = 0;
 }
 
@@ -1739,6 +1742,76 @@ int bloomhip_flush_batch(const void *ops, size_t n, int ops_on_device, int drop_
         HIP_TRY(hipStreamSynchronize(s));
     }
     *n_out = (size_t)kept;
+    return BLOOMHIP_OK;
+}
+
+int bloomhip_flush_cuts(const void *ops, size_t n, int ops_on_device, uint64_t buffer_max_entries,
+                        uint64_t *cuts, size_t cuts_cap, size_t *ncuts_out, int device,
+                        void *stream) {
+    g_last_error.clear();
+    const uint64_t B = buffer_max_entries;
+    if (!ncuts_out || B == 0) return BLOOMHIP_EINVAL;
+    if (n && !ops) return BLOOMHIP_EINVAL;
+    if (n && (reinterpret_cast<uintptr_t>(ops) & (ops_on_device ? 7 : 3))) return BLOOMHIP_EINVAL;
+    if (cuts_cap && !cuts) return BLOOMHIP_EINVAL;
+    if (n >= 0xFFFFFFFFull) return BLOOMHIP_ERANGE;  // 32-bit op indices, as bloomhip_flush_batch
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return BLOOMHIP_ENODEV;
+    if (device < 0 || device >= ndev) return BLOOMHIP_EINVAL;
+    *ncuts_out = 0;
+    if (n <= B) return BLOOMHIP_OK;  // the buffer never refuses: nothing is launched
+    DeviceGuard g(device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const LockedWorkspace w(device, s);
+    int rc = compact_reserve(w.get(), n, 1, false, s);
+    if (rc) return rc;
+    HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->fcount), &w->fcount_bytes,
+                         flush_workspace_words(n) * 4, s));
+    HIP_TRY(grow_touched(reinterpret_cast<void **>(&w->tcut), &w->tcut_bytes,
+                         cut_workspace_words(n, B) * 4, s));
+    // host ops are staged where the sort's first pass writes, after the
+    // records are taken from them
+    const void *src = ops;
+    if (!ops_on_device) {
+        HIP_TRY(hipMemcpyAsync(w->mbuf[1], ops, n * 8, hipMemcpyHostToDevice, s));
+        src = w->mbuf[1];
+    }
+    hipError_t e = launch_cut_records(src, n, w->mbuf[0], s);
+    if (e != hipSuccess) return fail_hip(e, "cut records launch");
+    // {key, index} sorted stably on the key: the batched PUT's sort, front to
+    // back, so the ops of one key stay in arrival order
+    uint32_t hist[kFlushPasses * kFlushBins];
+    e = launch_flush_hist(w->mbuf[0], n, w->fcount, s);
+    if (e != hipSuccess) return fail_hip(e, "flush histogram launch");
+    HIP_TRY(hipMemcpyAsync(hist, w->fcount, sizeof hist, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const uint32_t passes = flush_pass_mask(hist, n);
+    const void *cur = w->mbuf[0];
+    for (int p = 0; p < kFlushPasses; p++) {
+        if (!(passes >> p & 1)) continue;
+        void *to = w->mbuf[cur == w->mbuf[0] ? 1 : 0];
+        e = launch_flush_pass(cur, n, false, p, to, w->fcount, s);
+        if (e != hipSuccess) return fail_hip(e, "flush pass launch");
+        cur = to;
+    }
+    uint32_t *prev = w->tcut, *count = w->tcut + n, *dcuts = w->tcut + n + 1;
+    const uint64_t dcap = cut_max_cuts(n, B);
+    e = launch_cut_links(cur, n, prev, s);
+    if (e != hipSuccess) return fail_hip(e, "cut links launch");
+    e = launch_cut_walk(prev, n, B, dcuts, (uint32_t)dcap, count, s);
+    if (e != hipSuccess) return fail_hip(e, "cut walk launch");
+    uint32_t nc = 0;
+    HIP_TRY(hipMemcpyAsync(&nc, count, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (nc > dcap) return fail_hip(hipErrorUnknown, "flush cut count out of range");
+    *ncuts_out = nc;
+    if (nc > cuts_cap) return BLOOMHIP_ERANGE;
+    if (nc) {
+        std::vector<uint32_t> h(nc);
+        HIP_TRY(hipMemcpyAsync(h.data(), dcuts, (size_t)nc * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (uint32_t k = 0; k < nc; k++) cuts[k] = h[k];
+    }
     return BLOOMHIP_OK;
 }
 

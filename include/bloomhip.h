@@ -341,11 +341,88 @@ int bloomhip_range_batch(const bloomhip_filter *const *runs, const void *const *
  * Buffer::put refuses once the buffer holds max_size distinct keys, even for
  * a key already in it (src/buffer.cpp:42), and the tree flushes then.  Here
  * the caller chooses the batch.  A larger batch gives the same GET and RANGE
- * answers (newest-wins is associative) but other run boundaries; finding the
- * reference's own cut points in an op stream is left to the caller. */
+ * answers (newest-wins is associative) but other run boundaries;
+ * bloomhip_flush_cuts below finds the reference's own cut points in an op
+ * stream, and bloomhip_tree_put_batch ingests a stream at them. */
 int bloomhip_flush_batch(const void *ops, size_t n, int ops_on_device, int drop_tombstones,
                          void *out_entries, size_t *n_out, int out_on_device,
                          bloomhip_filter *f, int device, void *stream);
+
+/* --- the reference's flush cut points in an op stream -----------------------
+ * Where LSMTree::put flushes (src/lsm_tree.cpp:104-139): Buffer::put replaces
+ * the value of a key the buffer holds and refuses every op, even one on a key
+ * it holds, once it holds buffer_max_entries distinct keys (src/buffer.cpp:
+ * 37-58); the tree then flushes and the refused op starts a new buffer.  A
+ * segment therefore ends right after the op that brought its B-th distinct
+ * key, and the cut is realised only if another op follows: a stream that ends
+ * exactly there leaves a full buffer and no flush.
+ * ops: n entry_t records in arrival order, as for bloomhip_flush_batch (host,
+ * 4-byte aligned, or on `device`, 8-byte aligned); only the keys matter.
+ * cuts[0..*ncuts_out): the realised cuts 0 < c_1 < c_2 < ... < n (host
+ * memory): segment k is ops[c_{k-1}, c_k) with c_0 = 0, and the tail
+ * ops[c_last, n) stays in the buffer.  *ncuts_out is always the true count;
+ * when it exceeds cuts_cap the call returns BLOOMHIP_ERANGE and writes nothing
+ * to cuts.  n <= buffer_max_entries has no cut and launches nothing.
+ * Synchronous.
+ * Checked before any HIP call, in this order: BLOOMHIP_EINVAL for ncuts_out ==
+ * NULL, buffer_max_entries == 0, a NULL or misaligned ops with n > 0, cuts ==
+ * NULL with cuts_cap > 0; BLOOMHIP_ERANGE for n >= 2^32 - 1.  Then
+ * BLOOMHIP_ENODEV without a GPU and BLOOMHIP_EINVAL for a bad device. */
+int bloomhip_flush_cuts(const void *ops, size_t n, int ops_on_device,
+                        uint64_t buffer_max_entries, uint64_t *cuts, size_t cuts_cap,
+                        size_t *ncuts_out, int device, void *stream);
+
+/* --- the LSM tree handle ----------------------------------------------------
+ * LSMTree (src/lsm_tree.cpp:28-139) with batched ingest.  After any sequence
+ * of bloomhip_tree_put_batch calls the handle holds exactly the tree the
+ * reference holds after the same ops put one by one: the same runs in the same
+ * levels with the same entries, filter bits and fences, and the same buffer.
+ * Level l holds up to `fanout` runs of capacity buffer_max_entries *
+ * fanout^l; a run's filter has bloomhip_m_bits(that capacity, bits_per_entry)
+ * bits (src/lsm_tree.cpp:28-42, src/run.cpp:13-15).  The cascade of flushes
+ * and merge_downs (:44-102) is not replayed: every run the tree holds after a
+ * batch is built once, from one contiguous slice of the op stream and the old
+ * runs that end in it (newest-wins is associative).  Tombstones are kept by a
+ * flush and dropped only by a merge into the last level (:84-86).
+ * Calls on one tree serialise on a lock of the tree and are synchronous.
+ *
+ * bloomhip_tree_create: BLOOMHIP_EINVAL for out == NULL, buffer_max_entries ==
+ * 0, depth < 1, fanout < 1 or bloomhip_m_bits(buffer_max_entries,
+ * bits_per_entry) == 0 (the reference divides by zero there); BLOOMHIP_ERANGE
+ * for depth * fanout + 1 > 64 (GET and RANGE take at most 64 runs) or a level
+ * capacity past int64; all before any HIP call.
+ * bloomhip_tree_put_batch: ops as for bloomhip_flush_batch; *nflushes_out
+ * (optional) = the number of flushes the reference makes on them.  When the
+ * reference would die with "No more space in tree" the call returns
+ * BLOOMHIP_ERANGE; after that, or any other error, the tree is as it was.
+ * BLOOMHIP_ERANGE also when buffer + ops reach 2^32 - 1 entries.
+ * bloomhip_tree_get_batch, bloomhip_tree_range_batch: bloomhip_get_batch and
+ * bloomhip_range_batch over the buffer and then the runs in LSMTree::get_run
+ * order (level 0 newest to oldest, then level 1, ...; :141-151), with their
+ * output contracts and their documented deviation (the reference's 4096-byte
+ * page window).  found_run[i] is -1 for no run, 0 for the buffer and 1 + r
+ * for run r in get_run order, empty runs counted.
+ * bloomhip_tree_shape: runs per level (depth values) and the buffer's entries.
+ * bloomhip_tree_run: run `index` (0 = newest) of `level`, or the buffer
+ * (level -1, index 0, as a key-sorted run): its filter, its entries on the
+ * device and their number, all owned by the tree and valid until its next
+ * put_batch or destroy.  A run that ended with no entries (everything dropped
+ * at the last level) still occupies its slot. */
+typedef struct bloomhip_tree bloomhip_tree;
+int bloomhip_tree_create(int device, uint64_t buffer_max_entries, int depth, int fanout,
+                         float bits_per_entry, bloomhip_tree **out);
+int bloomhip_tree_destroy(bloomhip_tree *t);
+int bloomhip_tree_put_batch(bloomhip_tree *t, const void *ops, size_t n, int ops_on_device,
+                            size_t *nflushes_out, void *stream);
+int bloomhip_tree_get_batch(const bloomhip_tree *t, const void *keys, size_t n, size_t stride_bytes,
+                            int keys_on_device, int32_t *vals, int32_t *found_run,
+                            int out_on_device, void *stream);
+int bloomhip_tree_range_batch(const bloomhip_tree *t, const int32_t *starts, const int32_t *ends,
+                              size_t nq, int bounds_on_device, uint64_t *offsets, void *out_entries,
+                              size_t out_capacity, size_t *total_out, int out_on_device, void *stream);
+int bloomhip_tree_shape(const bloomhip_tree *t, uint32_t *runs_per_level, uint64_t *memtable_entries);
+int bloomhip_tree_run(const bloomhip_tree *t, int level, int index, const bloomhip_filter **f_out,
+                      const void **entries_dev_out, size_t *nentries_out);
 
 /* Scalar compatibility entry points (one key; synchronous), for
  * BloomFilter::set (src/bloom_filter.cpp:49-53) and is_set (:55-59) called
@@ -399,6 +476,25 @@ int bloomhip_trim(void);
  * the same inline functions the kernels run — evaluated on the host.
  * out[3*i + j] = hash_{j+1}(keys[i]) % m. */
 int bloomhip_host_positions(uint64_t m, const int32_t *keys, size_t n, uint64_t *out);
+
+/* Self-test hook (no GPU needed): the plan bloomhip_tree_put_batch builds its
+ * runs by.  Given the runs per level before a batch (depth values, each at
+ * most fanout) and the number of flushes the batch makes, the flushes and
+ * merge_downs (src/lsm_tree.cpp:44-139) are simulated on shapes only.  The
+ * plan is flat int32 records, one per run of the final tree, level by level,
+ * newest first:
+ *     level, first_new_segment, n_new_segments, n_old,
+ *     then n_old pairs (old_level, old_index), the newest old run first
+ * (old_index counts from the newest run of its level before the batch).  The
+ * run is the newest-wins merge of new segments [first, first + n_new) of the
+ * op stream, all newer than its old runs; n_new_segments = 0 with one old run
+ * of the same level means "kept as it is".  *plan_len_out = the int32 values
+ * the plan takes.  BLOOMHIP_ERANGE when the reference would die with "No more
+ * space in tree" (*plan_len_out = 0), and when plan_cap is too small
+ * (*plan_len_out valid, nothing written). */
+int bloomhip_tree_plan_host(const uint32_t *runs_per_level, int depth, int fanout,
+                            uint64_t nflushes, int32_t *plan, size_t plan_cap,
+                            size_t *plan_len_out);
 
 #ifdef __cplusplus
 }
