@@ -41,6 +41,12 @@ uint64_t compact_count_words(uint64_t n);
 // kway_workspace_bytes(n, k), 16-B aligned.
 constexpr int kKwayMaxRuns = 8;
 uint64_t kway_workspace_bytes(const uint64_t *n, int k);
+// The partitions of such a compaction (0 when every run is empty), and where
+// in ws launch_compact_kway puts their bounds, in bytes: kway_parts + 1 rows
+// of kKwayMaxRuns u32, row p column r = the first entry of run r in partition
+// p (row kway_parts: the runs' lengths); columns k and up are not written.
+uint64_t kway_parts(const uint64_t *n, int k);
+uint64_t kway_bounds_offset(const uint64_t *n, int k);
 hipError_t launch_compact_kway(const void *const *runs, const uint64_t *n, int k, int drop,
                                void *out, int32_t *keys_out, void *ws, uint32_t *count_out,
                                hipStream_t stream);

@@ -282,7 +282,10 @@ __global__ void __launch_bounds__(kCompactBlock) k_compact_write(
 // runs' samples) pick every q-th sample as a partition start, and the
 // start's position in each run is found by a binary search between two of
 // that run's samples.  A partition holds exactly q samples, so at most
-// (q + k) * kKwayS entries: with q = kKwayCap / kKwayS - k it fits one
+// (q + k) * kKwayS entries (exactly: q * kKwayS + (k - 1) * (kKwayS - 1), the
+// entries behind its q samples and, of every run but the one its start is a
+// sample of, the tail behind the last sample before the start;
+// tests/test_gpu_compact_edges.py reaches it): with q = kKwayCap / kKwayS - k it fits one
 // workgroup's LDS whatever the key distribution or duplicates (q fixed at 8
 // for every k left a fan-in-4 partition half full on average: twice the
 // partitions, each paying the ticket, bounds and look-back latencies).  k_kway_merge merges a partition's k shares in
@@ -722,13 +725,26 @@ uint64_t kway_parts(const uint64_t *n, int k) {
     return ns ? (ns - 1) / kway_q(k) + 1 : 0;
 }
 
-uint64_t kway_workspace_bytes(const uint64_t *n, int k) {
+namespace {
+// The workspace, in bytes from its 16-B aligned start:
+// samples (ns i32) | bounds (np + 1 rows) | status (np u64) + ticket | end
+struct KwayLayout {
+    uint64_t bounds, status, end;
+};
+KwayLayout kway_layout(const uint64_t *n, int k) {
     uint64_t ns = 0;
     for (int r = 0; r < k; r++) ns += (n[r] + kKwayS - 1) / kKwayS;
     const uint64_t np = kway_parts(n, k);
-    // samples | bounds (np + 1 rows) | status (np) + ticket + count
-    return ((ns * 4 + 15) & ~15ull) + (np + 1) * kKwayMaxRuns * 4 + 16 + np * 8 + 16;
+    KwayLayout l{};
+    l.bounds = (ns * 4 + 15) & ~15ull;
+    l.status = (l.bounds + (np + 1) * kKwayMaxRuns * 4 + 15) & ~15ull;
+    l.end = l.status + np * 8 + 16;
+    return l;
 }
+}  // namespace
+
+uint64_t kway_bounds_offset(const uint64_t *n, int k) { return kway_layout(n, k).bounds; }
+uint64_t kway_workspace_bytes(const uint64_t *n, int k) { return kway_layout(n, k).end; }
 
 hipError_t launch_compact_kway(const void *const *runs, const uint64_t *n, int k, int drop,
                                void *out, int32_t *keys_out, void *ws, uint32_t *count_out,
@@ -748,13 +764,11 @@ hipError_t launch_compact_kway(const void *const *runs, const uint64_t *n, int k
     R.soff[k] = ns;
     const uint64_t np = kway_parts(n, k);
     if (np == 0 || np >= (1ull << 31)) return hipErrorInvalidValue;
-    char *b = reinterpret_cast<char *>(ws);
+    const KwayLayout l = kway_layout(n, k);
+    char *b = reinterpret_cast<char *>(ws);  // 16-B aligned
     int32_t *skeys = reinterpret_cast<int32_t *>(b);
-    b += (ns * 4 + 15) & ~15ull;
-    uint32_t *bounds = reinterpret_cast<uint32_t *>(b);
-    b += (np + 1) * kKwayMaxRuns * 4;
-    b = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(b) + 15) & ~(uintptr_t)15);
-    uint64_t *status = reinterpret_cast<uint64_t *>(b);
+    uint32_t *bounds = reinterpret_cast<uint32_t *>(b + l.bounds);
+    uint64_t *status = reinterpret_cast<uint64_t *>(b + l.status);
     uint32_t *ticket = reinterpret_cast<uint32_t *>(status + np);
     const unsigned gs = (unsigned)((ns + 255) / 256);
     if ((uint64_t)gs * 256 < np) return hipErrorInvalidValue;  // the samples launch zeroes status

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <numeric>
+#include <vector>
 
 // the product kernels and launch templates, for ablation builds
 #include "bloom_combine.h"
@@ -1147,4 +1148,87 @@ extern "C" int ubench_transpose2(int tr, const void *rows, void *cols, size_t nt
     if (tr == 64) ub_transpose2<64><<<grid, 256, 0, s>>>(r, c, ntiles, width, cstride);
     else ub_transpose2<128><<<grid, 256, 0, s>>>(r, c, ntiles, width, cstride);
     return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// ---------------------------------------------------------------------------
+// The compaction's launches, forced one at a time on the caller's device
+// buffers (tests/test_gpu_compact_edges.py): each allocates and frees its own
+// workspace, runs on the null stream, synchronises it before returning and
+// returns the HIP error as an int (0 = hipSuccess).  runs / a / b / out and the
+// length arrays are host arrays of device pointers and of entry counts.
+// ---------------------------------------------------------------------------
+namespace {
+// a call's workspace, freed on every way out
+struct UbScratch {
+    void *p = nullptr;
+    hipError_t alloc(uint64_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
+    ~UbScratch() {
+        if (p) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+// launch_compact_kway (k_kway_samples, k_kway_split, k_kway_merge) of k runs,
+// newest first.  out: sum(n) entries; keys_out (optional): sum(n) int32.
+// Host results: bounds_out = the partition bounds, (*nparts_out + 1) rows of
+// kKwayMaxRuns u32 as launch_compact_kway leaves them in its workspace
+// (kway_bounds_offset; columns k and up unwritten), sized by the caller for
+// at least sum(ceil(n[r] / 256)) + 1 rows; *count_out = the kept count.
+extern "C" int ubench_kway_compact(const void *const *runs, const uint64_t *n, int k, int drop,
+                                   void *out, int32_t *keys_out, uint32_t *bounds_out,
+                                   uint64_t *nparts_out, uint32_t *count_out) {
+    if (k < 1 || k > kKwayMaxRuns) return (int)hipErrorInvalidValue;
+    const uint64_t np = kway_parts(n, k);
+    const uint64_t wbytes = (kway_workspace_bytes(n, k) + 15) & ~15ull;
+    UbScratch ws;
+    hipError_t e = ws.alloc(wbytes + 16);  // + the kept count
+    if (e != hipSuccess) return (int)e;
+    char *w = static_cast<char *>(ws.p);
+    uint32_t *dcount = reinterpret_cast<uint32_t *>(w + wbytes);
+    e = launch_compact_kway(runs, n, k, drop, out, keys_out, w, dcount, nullptr);
+    if (e != hipSuccess) return (int)e;
+    e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return (int)e;
+    e = hipMemcpy(bounds_out, w + kway_bounds_offset(n, k), (np + 1) * kKwayMaxRuns * 4,
+                  hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return (int)e;
+    *nparts_out = np;
+    return (int)hipMemcpy(count_out, dcount, 4, hipMemcpyDeviceToHost);
+}
+
+// launch_merge_round (k_merge_split, k_merge_tile) of np pairs: out[p] = the
+// stable merge of a[p] (na[p] entries, wins ties) and b[p]; a, b 8-B aligned,
+// out 16-B aligned, na[p] + nb[p] entries.
+extern "C" int ubench_merge_round(const void *const *a, const uint64_t *na, const void *const *b,
+                                  const uint64_t *nb, void *const *out, int np) {
+    std::vector<MergePairArgs> pairs;
+    uint64_t total = 0;
+    for (int p = 0; p < np; p++) {
+        pairs.push_back({a[p], na[p], b[p], nb[p], out[p]});
+        total += na[p] + nb[p];
+    }
+    UbScratch ws;
+    hipError_t e = ws.alloc(merge_split_words(total) * 8);
+    if (e != hipSuccess) return (int)e;
+    e = launch_merge_round(pairs.data(), np, static_cast<uint64_t *>(ws.p), nullptr);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipStreamSynchronize(nullptr);
+}
+
+// launch_dedup (k_compact_count, k_scan_counts, k_compact_write) of n
+// key-sorted entries at `in` (16-B aligned: the kernels read entry pairs as
+// vectors).  out: n entries; keys_out (optional): n int32; *count_out (host)
+// = the kept count.
+extern "C" int ubench_dedup(const void *in, uint64_t n, int drop, void *out, int32_t *keys_out,
+                            uint32_t *count_out) {
+    if (reinterpret_cast<uintptr_t>(in) & 15) return (int)hipErrorInvalidValue;
+    UbScratch ws;
+    hipError_t e = ws.alloc(compact_count_words(n) * 4 + 4);
+    if (e != hipSuccess) return (int)e;
+    uint32_t *counts = static_cast<uint32_t *>(ws.p);
+    e = launch_dedup(in, n, drop, out, counts, nullptr, keys_out);
+    if (e != hipSuccess) return (int)e;
+    e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) return (int)e;
+    return (int)hipMemcpy(count_out, counts + compact_count_words(n) - 1, 4, hipMemcpyDeviceToHost);
 }

@@ -97,8 +97,11 @@ def test_compact_everything_dropped_leaves_an_empty_run(coracle):
 
 
 def test_compact_device_runs_at_odd_entry_offsets(coracle):
-    # device runs that start 8 B past a 16-B boundary: the merge stages each
-    # share in address-aligned 16-B vectors at the matching LDS parity
+    # device runs that start 8 B past a 16-B boundary.  With 4 runs this is the
+    # one-pass k-way kernel (k_kway_merge), which loads entries one by one
+    # and has no 16-B staging; the pairwise merge tile that stages each share
+    # in address-aligned 16-B vectors (stage_share) takes such runs in
+    # test_gpu_compact_edges.py::test_compact_many_device_runs_at_odd_address_parity
     torch = pytest.importorskip("torch")
     runs = make_runs([70_001, 33_333, 4097, 2], 2**31 - 1, 11)
     views = []
